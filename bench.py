@@ -12,6 +12,11 @@ Inputs are resident in HBM before the timed region: a pool of distinct
 collated batches, cycled so consecutive steps see different molecules.
 
 Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).
+
+A plain run sets up, warms up, times the steps and prints the line.  --full
+adds every other measurement (the event-timed kernel pass and its rooflines,
+the superbatch roofline, the CPU baselines, the fine-tune leg); --dump-outputs
+DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -714,6 +719,36 @@ def finetune_leg(a, dev):
                                  "cpu_baseline")}
 
 
+DUMP_LIMIT = 64 << 20  # bytes of one --dump-outputs directory
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every tensor of ``arrays`` as dirname/<name>.npy, float32
+    (float64 kept), scalars as one-element arrays.  An array above its share of
+    DUMP_LIMIT is written as a fixed sample of its elements (seeded indices,
+    ascending), so the directory stays within the limit."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT // max(len(arrays), 1)
+    for name, t in arrays.items():
+        arr = t.detach().cpu().numpy()
+        arr = np.atleast_1d(arr if arr.dtype == np.float64 else arr.astype(np.float32))
+        if arr.nbytes > share:
+            idx = np.random.default_rng(0).choice(arr.size, share // arr.itemsize, replace=False)
+            arr = arr.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+
+def step_outputs(losses, model, buffers):
+    """What a caller of the timed step holds after it: the step's loss parts
+    and the model it updated (parameters and the given BatchNorm buffers, each
+    flattened in module order)."""
+    out = {"loss_" + name: v for name, v in losses.items()}
+    out["params"] = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    if buffers:
+        out["bn_buffers"] = torch.cat([b.reshape(-1).float() for b in buffers])
+    return out
+
+
 def build_replay_step(model, opt, pool_host, k, batch, dev, prefetch=True, noise=None,
                       collective=False, reducer=None, warm=3, split=True, noise_prefetch=True,
                       fuse_adam=True):
@@ -931,6 +966,14 @@ def main():
     ap.add_argument("--k", type=int, default=1)
     ap.add_argument("--gin-layers", type=int, default=5)
     ap.add_argument("--pool", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement: the event-timed "
+                         "kernel pass (roofline, roofline_kernels), the superbatch roofline, the "
+                         "CPU baselines and the fine-tune leg; each still has its --no-* switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss parts, "
+                         "updated parameters, BatchNorm running statistics) as DIR/<name>.npy "
+                         "(rank 0; float32, at most 64 MB)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-superbatch", action="store_true")
@@ -980,6 +1023,8 @@ def main():
     ap.add_argument("--no-finetune", action="store_true",
                     help="skip the fine-tune leg (configs[4]) the N = 1 line carries in 'finetune'")
     a = ap.parse_args()
+    if not a.full:  # a plain run: the timed steps and their line only
+        a.no_kernel_timer = a.no_superbatch = a.no_cpu_baseline = a.no_finetune = True
     pkg.ops.STORE_R = not a.recompute_r
     pkg.ops.AGG_FREE = not a.no_agg_free
     if a.agg_free_min_rows is not None:
@@ -1164,6 +1209,10 @@ def main():
         dist.all_reduce(d, op=dist.ReduceOp.MAX)
         replica_diff = float(d.item())
     final_loss = float(sum(loss).item()) if isinstance(loss, tuple) else float(loss.item())
+    if a.dump_outputs and rank == 0:  # (before any later pass touches the model)
+        parts = dict(zip(("kl", "rec", "con"), loss)) if isinstance(loss, tuple) else {"total": loss}
+        dump_outputs(a.dump_outputs, step_outputs(parts, model, pkg.dist.bn_buffers(model)))
+        progress(f"outputs of the last timed step written to {a.dump_outputs}")
 
     # instrumented eager pass over the same batches: HIP events around every
     # launch of the measured kernel (forward+backward of the same model)

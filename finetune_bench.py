@@ -292,6 +292,9 @@ def run(bench, a, dev):
         pkg.ops.stamps_enable(dev, 0)
         pkg.ops._STAMPS["buf"] = None
     final_loss = float(static_loss.item())
+    if getattr(a, "dump_outputs", None):  # (bench.py --finetune molhiv --dump-outputs DIR)
+        outs = bench.step_outputs({"bce": static_loss}, ft, pkg.dist.bn_buffers(ft))
+        bench.dump_outputs(a.dump_outputs, dict(outs, scores=fs.scores))
     # kernel timer: eager fine-tune steps on one stream, HIP events per launch
     kernels = {}
     if not a.no_kernel_timer:

@@ -195,6 +195,41 @@ def test_bench_allreduce_captured_one_rank_rccl():
     assert line["value"] > 0 and line["config"]["final_loss"] == line["config"]["final_loss"]
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain bench run times --steps steps and carries none of the --full
+    measurements in its line; --dump-outputs writes the last timed step's loss
+    parts and the updated model as float32 arrays, the same from run to run."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for tag in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
+               "--warmup", "1", "--batch", "64", "--pool", "2", "--dump-outputs",
+               str(tmp_path / tag)]
+        out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=240)
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert line["unit"] == "graphs/s" and line["higher_is_better"] and line["dtype"] == "fp32"
+        assert abs(line["value"] - 64 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"]
+        for key in ("roofline", "roofline_kernels", "roofline_superbatch", "cpu_baseline",
+                    "finetune"):
+            assert line[key] is None, key
+        dumps.append({f[:-4]: np.load(tmp_path / tag / f) for f in os.listdir(tmp_path / tag)})
+    a, b = dumps
+    assert sorted(a) == ["bn_buffers", "loss_con", "loss_kl", "loss_rec", "params"]
+    for name, arr in a.items():
+        assert arr.dtype == np.float32 and np.isfinite(arr).all(), name
+        assert np.array_equal(arr, b[name]), name
+    assert a["loss_kl"].shape == (1,) and a["params"].size > 100_000
+    loss = float(a["loss_kl"][0] + a["loss_rec"][0] + a["loss_con"][0])
+    assert abs(loss - line["config"]["final_loss"]) <= 1e-3 + 1e-5 * abs(loss)
+
+
 def test_adam_step_reduce_matches_reduce_then_step(pkg, dev):
     """scgib_adam_step_reduce: the slab reduce of two jobs (one with a column
     stride) and the Adam step in one launch, bitwise the reduce launch

@@ -482,6 +482,30 @@ def test_bench_kernel_table_evaluates(pkg):
         assert b > 0 and f >= 0, name
 
 
+def test_bench_dump_outputs_format_and_limit(pkg, tmp_path, monkeypatch):
+    """bench.dump_outputs: one float32 .npy per name (float64 kept, a scalar as
+    one element), and an array above its share of DUMP_LIMIT written as the
+    same fixed sample of its elements on every call."""
+    import importlib
+    bench = importlib.import_module("bench")
+    x = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    arrays = {"half": torch.ones(3, 2, dtype=torch.float16), "scalar": torch.tensor(2.5), "x": x}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert sorted(os.listdir(tmp_path / "a")) == ["half.npy", "scalar.npy", "x.npy"]
+    assert got["half"].dtype == np.float32 and got["half"].shape == (3, 2)
+    assert got["scalar"].dtype == np.float32 and got["scalar"].tolist() == [2.5]
+    assert got["x"].dtype == np.float64 and np.array_equal(got["x"], x.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 3 * 800)  # 800 bytes each: x keeps 100 of 1000
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    xb, xc = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert xb.shape == (100,) and np.array_equal(xb, xc)
+    assert np.all(np.diff(xb) > 0) and set(xb.tolist()) <= set(range(1000))
+    assert np.array_equal(np.load(tmp_path / "b" / "half.npy"), got["half"])
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) < 3 * 800 + 3 * 256
+
+
 def test_xq_handoffs_off_under_serialised_dispatch(pkg, monkeypatch):
     """ops.XQ_FLAGS's default: the signal / wait hand-offs need concurrent
     queues, so they are off under PMC counter collection, kernel tracing or
