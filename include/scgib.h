@@ -154,6 +154,60 @@ int scgib_gin_aggregate(const float *h, const int32_t *rowptr, const int32_t *co
                         int64_t n_nodes, int32_t dim, float one_plus_eps, float *out,
                         const int32_t *dims, scgib_stream_t stream);
 
+/* ---- GCN / GraphSAGE encoders: one fused graph-convolution layer (ABI 23) ----
+ * Replaces DGL GraphConv(norm='both', allow_zero_in_degree=True) and
+ * SAGEConv(aggregator 'mean') of the reference's GCN / GraphSAGE encoders
+ * (models.py:75-104) and their autograd backward.  The DGL semantics are
+ * restated (DGL 1.1.0, environment.yml), not linked.
+ *
+ *   agg[v] = c_dst[v] * sum_{u -> v} c_src[u] x[u]     (dst-major CSR order)
+ *   out[v] = act(agg[v] Wn + x[v] Ws + b)              act = ReLU or identity
+ *
+ * scgib_conv_norm: the coefficient vectors [n] of a graph from its row
+ *   pointers, din[v] = rowptr[v+1] - rowptr[v], dout[u] likewise on rowptr_t:
+ *   mode 0 (GCN): c_src = max(dout,1)^-1/2, c_dst = max(din,1)^-1/2;
+ *   mode 1 (mean): c_src = 1, c_dst = 1 / max(din,1).  Either output may be
+ *   NULL (not written); rows >= dims[0] are written as zeros.
+ * scgib_conv_layer_fwd: c_src / c_dst may each be NULL (= 1).  Two layer
+ *   kinds, told apart by w_self:
+ *     w_self NULL, w_in_major = 1: GraphConv — w_neigh is [d_in][d_out]
+ *       (GraphConv.weight's layout), no self term;
+ *     w_self given, w_in_major = 0: SAGEConv — w_neigh (fc_neigh.weight) and
+ *       w_self (fc_self.weight) are [d_out][d_in] (nn.Linear's layout).
+ *   Any other combination: SCGIB_EUNSUPPORTED.  bias [d_out] may be NULL.
+ *   Writes agg [n][d_in] (saved for the backward; may be NULL) and
+ *   out [n][d_out].  (d_in, d_out) in {(32,128), (128,128), (128,64), (32,64),
+ *   (64,64)}, else SCGIB_EUNSUPPORTED.  The weights are read in place: no
+ *   transposed copy is made.
+ * scgib_conv_layer_bwd: with dz = dout * [out > 0] (out given: the layer had
+ *   a ReLU; dz [n][d_out] is then written) or dz = dout (out NULL),
+ *     dWn = agg^T dz, dWs = x^T dz, db = sum_v dz[v]   into scgib_conv_slabs(n)
+ *     per-workgroup slabs of scgib_conv_slab_width(d_in, d_out, has_self)
+ *     floats: dWn | dWs (has_self) | db, each weight block in the weight's own
+ *     layout — the caller sums them with scgib_slab_reduce_multi;
+ *     dx[u] = c_src[u] sum_{u -> v} c_dst[v] (dz[v] Wn^T) + dz[u] Ws^T over the
+ *     transposed CSR (rowptr_t, col_t), times [x[u] > 0] when mask_x (x is the
+ *     previous layer's ReLU output: dx is then that layer's dz).  dx NULL: the
+ *     input needs no gradient, only the slabs are produced.
+ *   c_src / c_dst are the FORWARD's vectors (the kernel swaps their roles).
+ * Capacity mode: rows >= dims[0] of agg / out / dz / dx are zeros and do not
+ * contribute to the slabs. */
+int scgib_conv_norm(const int32_t *rowptr, const int32_t *rowptr_t, int64_t n_nodes, int32_t mode,
+                    float *c_src, float *c_dst, const int32_t *dims, scgib_stream_t stream);
+int64_t scgib_conv_slabs(int64_t n_nodes);
+int64_t scgib_conv_slab_width(int32_t d_in, int32_t d_out, int32_t has_self);
+int scgib_conv_layer_fwd(const float *x, const int32_t *rowptr, const int32_t *col,
+                         const float *c_src, const float *c_dst, int64_t n_nodes, int32_t d_in,
+                         int32_t d_out, const float *w_neigh, const float *w_self,
+                         int32_t w_in_major, const float *bias, int32_t relu, float *agg,
+                         float *out, const int32_t *dims, scgib_stream_t stream);
+int scgib_conv_layer_bwd(const float *dout, const float *out, const float *agg, const float *x,
+                         const int32_t *rowptr_t, const int32_t *col_t, const float *c_src,
+                         const float *c_dst, int64_t n_nodes, int32_t d_in, int32_t d_out,
+                         const float *w_neigh, const float *w_self, int32_t w_in_major,
+                         int32_t mask_x, float *dz, float *dx, float *slab, const int32_t *dims,
+                         scgib_stream_t stream);
+
 /* ---- A5 fused: one GIN layer = GINConv(MLP) + BatchNorm1d + ReLU -----------
  * Replaces, per layer, DGL GINConv + nn.Linear x2 + ReLU + nn.BatchNorm1d +
  * F.relu of GIN.forward (models.py:63-71) and their autograd backward.

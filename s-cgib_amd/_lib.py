@@ -42,6 +42,13 @@ SIGNATURES = {
                                               _P]),
     "scgib_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "scgib_gin_aggregate": (ctypes.c_int, [_P, _P, _P, _I64, _I32, _F, _P, _P, _P]),
+    "scgib_conv_norm": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P]),
+    "scgib_conv_slabs": (_I64, [_I64]),
+    "scgib_conv_slab_width": (_I64, [_I32, _I32, _I32]),
+    "scgib_conv_layer_fwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I32, _P,
+                                            _I32, _P, _P, _P, _P]),
+    "scgib_conv_layer_bwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P,
+                                            _P, _I32, _I32, _P, _P, _P, _P, _P]),
     "scgib_segment_sum": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     "scgib_segment_broadcast": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I64, _P, _P]),
     "scgib_egonet_workspace_bytes": (_I64, [_I64]),
@@ -194,7 +201,7 @@ class RunningUpdate(ctypes.Structure):
                 ("num_batches_tracked", ctypes.c_void_p)]
 
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 STATS_STRIDE = 260
 PGRAD_STRIDE = 324
 HIDDEN = 64

@@ -5,6 +5,8 @@ constructor/forward signatures and the same ``state_dict`` keys:
 
   MLP ................ models.py:38-49
   GIN ................ models.py:52-72   (GINConv sum aggregation -> HIP kernel)
+  GCN, GraphSAGE ..... models.py:75-104  (GraphConv / SAGEConv layers -> the
+                                          fused HIP layer of conv_layer.hip)
   Mainmodel .......... models.py:546-782 (forward :662-700,
                                           extract_features :702-750)
   Mainmodel_continue . models.py:1010-1276 (the wrapper exp_pretraining.py
@@ -26,8 +28,12 @@ Differences from the reference, all deliberate:
   * ``flatten_batch_subgraphs`` may be ``None``: the ego-nets are then built
     on the device from ``batch_g`` (scgib_egonet_*), replacing the offline
     khop_in_subgraph pass and the per-step dgl.batch of the reference;
-  * only the GIN encoder is implemented (the north-star path); GCN /
-    GraphSAGE / Transformer encoders raise.
+  * encoders: "GIN" (the north-star path, with its fused pair / fold /
+    deferred-reduce machinery), "GCN" and "GraphSAGE" (each layer one fused
+    HIP launch forward and two backward, run through the plain two-stream
+    encoder branch; DGL 1.1.0's GraphConv / SAGEConv semantics restated, not
+    linked) in Mainmodel and Mainmodel_continue; "Transformer" raises, and
+    the fine-tune / domain-adaptation heads take "GIN" only.
 """
 from __future__ import annotations
 
@@ -104,6 +110,137 @@ class GIN(nn.Module):
         for conv, bn in zip(self.ginlayers, self.batch_norms):
             h = F.relu(bn(conv(g, h)))
         return h
+
+
+class GraphConv(nn.Module):
+    """DGL GraphConv(in, out, norm='both', weight=True, bias=True): symmetric
+    degree normalisation (degrees clamped to 1), ``weight`` stored [in, out],
+    xavier-uniform; zero ``bias``.  A node without in-edges gets its bias
+    (allow_zero_in_degree is accepted and never refuses a graph)."""
+
+    def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True, activation=None,
+                 allow_zero_in_degree=False):
+        super().__init__()
+        if norm != "both" or not weight or not bias:
+            raise NotImplementedError("only the reference's GraphConv(norm='both', weight, bias)")
+        self._in_feats, self._out_feats = in_feats, out_feats
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self._activation = activation
+        self.weight = nn.Parameter(torch.empty(in_feats, out_feats))
+        self.bias = nn.Parameter(torch.empty(out_feats))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.xavier_uniform_(self.weight)
+        nn.init.zeros_(self.bias)
+
+    def conv_params(self):
+        return self.weight, None, self.bias
+
+    def forward(self, graph, feat, weight=None, edge_weight=None):
+        if weight is not None or edge_weight is not None:
+            raise NotImplementedError("GraphConv: external weight / edge_weight")
+        rst = ops.conv_layer(feat, graph, self.weight, None, self.bias, "gcn", False)
+        return rst if self._activation is None else self._activation(rst)
+
+
+class SAGEConv(nn.Module):
+    """DGL SAGEConv(in, out, 'mean'): fc_self(x_v) + fc_neigh(mean of the
+    in-neighbours, 0 without any) + bias; both linears [out, in] without a
+    bias of their own (xavier-uniform, ReLU gain), ``bias`` [out] zero.  An
+    older file's ``fc_self.bias`` loads as ``bias``."""
+
+    def __init__(self, in_feats, out_feats, aggregator_type, feat_drop=0.0, bias=True, norm=None,
+                 activation=None):
+        super().__init__()
+        if aggregator_type != "mean" or feat_drop or not bias or norm is not None:
+            raise NotImplementedError("only the reference's SAGEConv(in, out, 'mean')")
+        self._in_src_feats = self._in_dst_feats = in_feats
+        self._out_feats = out_feats
+        self._aggre_type = aggregator_type
+        self.activation = activation
+        self.fc_neigh = nn.Linear(in_feats, out_feats, bias=False)
+        self.fc_self = nn.Linear(in_feats, out_feats, bias=False)
+        self.bias = nn.Parameter(torch.zeros(out_feats))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
+        nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
+        nn.init.zeros_(self.bias)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        old = prefix + "fc_self.bias"  # (this module loads before its children see the key)
+        if old in state_dict and prefix + "bias" not in state_dict:
+            state_dict[prefix + "bias"] = state_dict.pop(old)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def conv_params(self):
+        return self.fc_neigh.weight, self.fc_self.weight, self.bias
+
+    def forward(self, graph, feat, edge_weight=None):
+        if edge_weight is not None:
+            raise NotImplementedError("SAGEConv: edge_weight")
+        rst = ops.conv_layer(feat, graph, self.fc_neigh.weight, self.fc_self.weight, self.bias,
+                             "mean", False)
+        return rst if self.activation is None else self.activation(rst)
+
+
+class GCN(nn.Module):
+    """GCN encoder (models.py:75-88): conv1 (d -> 2H), ReLU, conv2 (2H -> 2H),
+    ReLU, conv3 (2H -> H); no BatchNorm, no activation after conv3."""
+
+    conv_mode = "gcn"
+    fused = False  # not the fused GIN machinery (the fold gate of _encode_forked)
+
+    def __init__(self, num_features, hidden_dim=64):
+        super().__init__()
+        self.conv1 = GraphConv(num_features, hidden_dim * 2, allow_zero_in_degree=True)
+        self.conv2 = GraphConv(hidden_dim * 2, hidden_dim * 2, allow_zero_in_degree=True)
+        self.conv3 = GraphConv(hidden_dim * 2, hidden_dim, allow_zero_in_degree=True)
+
+    def layer_sequence(self):
+        return [(self.conv1, True), (self.conv2, True), (self.conv3, False)]
+
+    def forward(self, g, in_feat):
+        return ops.conv_encoder(in_feat, g, self)
+
+
+class GraphSAGE(nn.Module):
+    """GraphSAGE encoder (models.py:91-104), with the reference's forward kept
+    literally: conv1, ReLU, conv2, ReLU, conv2 AGAIN (models.py:103) — conv3
+    is built (its keys are in the state_dict) and never used, so its
+    gradients stay None and conv2's are the sum over its two uses."""
+
+    conv_mode = "mean"
+    fused = False
+
+    def __init__(self, in_feats, h_feats):
+        super().__init__()
+        self.conv1 = SAGEConv(in_feats, h_feats, "mean")
+        self.conv2 = SAGEConv(h_feats, h_feats, "mean")
+        self.conv3 = SAGEConv(h_feats, h_feats, "mean")
+
+    def layer_sequence(self):
+        return [(self.conv1, True), (self.conv2, True), (self.conv2, False)]
+
+    def forward(self, g, in_feat):
+        return ops.conv_encoder(in_feat, g, self)
+
+
+ENCODERS = ("GIN", "GCN", "GraphSAGE")
+
+
+def _make_encoder(encoder, in_dim, hidden_dim, args):
+    """One encoder of Mainmodel / Mainmodel_continue (models.py:573-587)."""
+    if encoder == "GIN":
+        return GIN(in_dim, hidden_dim, _gin_layers(args))
+    if encoder == "GCN":
+        return GCN(in_dim, hidden_dim)
+    if encoder == "GraphSAGE":
+        return GraphSAGE(in_dim, hidden_dim)
+    raise NotImplementedError(f"encoder {encoder!r}: implemented are {', '.join(ENCODERS)}")
 
 
 class Set2Set(nn.Module):
@@ -406,10 +543,9 @@ class Mainmodel(_SCGIBCore):
         self.reconstructX = nn.Sequential(nn.Linear(self.hidden_dim, self.in_dim))
         self.MLP = nn.Sequential(nn.Linear(2 * hidden_dim, hidden_dim), nn.ReLU(),
                                  nn.Linear(hidden_dim, hidden_dim))
-        if encoder != "GIN":
-            raise NotImplementedError(f"encoder {encoder!r}: only GIN is on the hot path")
-        self.Encoder1 = GIN(self.in_dim, hidden_dim, _gin_layers(args))
-        self.Encoder2 = GIN(self.in_dim, hidden_dim, _gin_layers(args))
+        self.encoder_name = encoder
+        self.Encoder1 = _make_encoder(encoder, self.in_dim, hidden_dim, args)
+        self.Encoder2 = _make_encoder(encoder, self.in_dim, hidden_dim, args)
         self.compressor = nn.Sequential(nn.Linear(hidden_dim, hidden_dim),
                                         nn.BatchNorm1d(hidden_dim), nn.ReLU(),
                                         nn.Linear(hidden_dim, 1))
@@ -480,10 +616,9 @@ class Mainmodel_continue(_SCGIBCore):
                                      nn.Linear(hidden_dim, out_dim))
         self.MLP = nn.Sequential(nn.Linear(2 * hidden_dim, hidden_dim), nn.ReLU(),
                                  nn.Linear(hidden_dim, hidden_dim))
-        if encoder != "GIN":
-            raise NotImplementedError(f"encoder {encoder!r}: only GIN is on the hot path")
-        self.Encoder1 = GIN(self.in_dim, hidden_dim, _gin_layers(args))
-        self.Encoder2 = GIN(self.in_dim, hidden_dim, _gin_layers(args))
+        self.encoder_name = encoder
+        self.Encoder1 = _make_encoder(encoder, self.in_dim, hidden_dim, args)
+        self.Encoder2 = _make_encoder(encoder, self.in_dim, hidden_dim, args)
         self.model = load_checkpoint(cp_filename, args)
         for p in self.model.parameters():
             p.requires_grad = True
@@ -788,11 +923,14 @@ def save_checkpoint(model, path, args=None, in_dim=None, num_classes=1):
         cfg = {k: getattr(args, k) for k in _CKPT_ARGS if hasattr(args, k)}
     cfg.update(kind=type(model).__name__, in_dim=in_dim, hidden_dim=model.hidden_dim,
                k_transition=model.k_transition, num_classes=num_classes)
-    levels, m = [], model  # the wrapper chain (continue / DA around a Mainmodel)
+    levels, encoders, m = [], [], model  # the wrapper chain (continue / DA around a Mainmodel)
     while m is not None:
         levels.append([type(m).__name__, int(m.transfer_d.weight.shape[1])])
+        encoders.append(str(getattr(m, "encoder_name", "GIN")))
         m = getattr(m, "model", None)
     cfg["levels"] = levels
+    # the encoder of each level (files without the entry: GIN at every level)
+    cfg["encoder"], cfg["encoders"] = encoders[0], encoders
     torch.save({"config": cfg, "state_dict": model.state_dict()}, path)
 
 
@@ -831,16 +969,19 @@ def model_from_state(levels, cfg, sd, args=None):
     return m
 
 
-def _build_levels(levels, ns, cfg):
+def _build_levels(levels, ns, cfg, depth=0):
     """An untrained module for load_state_dict: levels = [(kind, F), ...] from
-    the outermost wrapper down to the Mainmodel it wraps."""
+    the outermost wrapper down to the Mainmodel it wraps; each level's encoder
+    from cfg["encoders"] (cfg["encoder"] for all, "GIN" in files without)."""
     (kind, f_in), rest = levels[0], levels[1:]
     dims = (f_in, cfg["hidden_dim"], 4, 4, cfg["k_transition"])
+    encs = cfg.get("encoders") or []
+    enc = str(encs[depth]) if depth < len(encs) else str(cfg.get("encoder", "GIN"))
     if kind == "Mainmodel":
-        return Mainmodel(ns, *dims, "GIN")
-    inner = _build_levels(rest or [("Mainmodel", f_in)], ns, cfg)
+        return Mainmodel(ns, *dims, enc)
+    inner = _build_levels(rest or [("Mainmodel", f_in)], ns, cfg, depth + 1)
     if kind == "Mainmodel_continue":
-        return Mainmodel_continue(ns, *dims, cfg.get("num_classes", 1), inner, "GIN")
+        return Mainmodel_continue(ns, *dims, cfg.get("num_classes", 1), inner, enc)
     if kind == "Mainmodel_domainadapt":
-        return Mainmodel_domainadapt(ns, *dims, cfg.get("num_classes", 1), inner, "GIN")
+        return Mainmodel_domainadapt(ns, *dims, cfg.get("num_classes", 1), inner, enc)
     raise NotImplementedError(f"checkpoint kind {kind!r}")

@@ -2265,3 +2265,127 @@ def recon_logm(im, graph, logm):
     if not isinstance(logm, _graph.LogMBatch):
         logm = _graph.LogMBatch(list(logm), im.device)
     return _ReconLogM.apply(im, graph, logm)
+
+
+# ---------------------------------------------------------------------------
+# GCN / GraphSAGE encoders: the fused graph-convolution layer
+# (csrc/conv_layer.hip; DGL GraphConv(norm='both') / SAGEConv('mean') restated)
+# ---------------------------------------------------------------------------
+CONV_MODES = {"gcn": 0, "mean": 1}
+
+
+def _conv_mode(mode):
+    m = str(mode).lower()
+    if m not in CONV_MODES:
+        raise _lib.ScgibError(f"conv_layer: mode {mode!r} (expected 'gcn' or 'mean')")
+    return m
+
+
+def conv_norm(graph, mode):
+    """(c_src, c_dst) of ``graph`` for ``mode``: 'gcn' max(deg, 1)^-1/2 on both
+    sides, 'mean' (None, 1 / max(in-degree, 1)).  One device launch per call and
+    never cached on the graph: a StaticBatch's contents change under replay."""
+    mode = _conv_mode(mode)
+    n, dev = graph.num_nodes(), graph.rowptr.device
+    if not graph.rowptr.is_cuda:
+        raise _lib.ScgibError("conv_norm: the graph is not on the HIP device (no CPU fallback)")
+    c_dst = torch.empty(n, dtype=torch.float32, device=dev)
+    c_src = torch.empty(n, dtype=torch.float32, device=dev) if mode == "gcn" else None
+    _lib.call("scgib_conv_norm", _p(graph.rowptr), _p(graph.rowptr_t), n, CONV_MODES[mode],
+              _p(c_src), _p(c_dst), _p(graph.dims), _stream())
+    return c_src, c_dst
+
+
+class _ConvLayer(torch.autograd.Function):
+    """out = act(agg Wn + x Ws + b), agg[v] = c_dst[v] sum_{u->v} c_src[u] x[u].
+
+    'gcn': w_neigh [in, out] (GraphConv.weight), no w_self; 'mean': w_neigh /
+    w_self [out, in] (the SAGE linears).  ``mask_in``: x is the previous conv
+    layer's ReLU output and that layer takes this one's dx as its dz (the dx
+    kernel applies [x > 0]); ``premasked``: the incoming gradient is such a dz
+    already.  conv_encoder sets the two on the private activations between its
+    layers; conv_layer leaves both off."""
+
+    @staticmethod
+    def forward(ctx, x, w_neigh, w_self, bias, graph, mode, relu, norm, mask_in, premasked):
+        x = _f32(x, "conv_layer")
+        n, d_in = x.shape
+        gcn = mode == "gcn"
+        if gcn != (w_self is None):
+            raise _lib.ScgibError("conv_layer: 'gcn' takes no w_self, 'mean' needs one")
+        d_out = int(w_neigh.shape[1] if gcn else w_neigh.shape[0])
+        want = (d_in, d_out) if gcn else (d_out, d_in)
+        if tuple(w_neigh.shape) != want or (w_self is not None and tuple(w_self.shape) != want) \
+                or (bias is not None and tuple(bias.shape) != (d_out,)):
+            raise _lib.ScgibError(f"conv_layer: weight shapes do not match x [{n}, {d_in}]")
+        if n != graph.num_nodes():
+            raise _lib.ScgibError("conv_layer: x rows != graph nodes")
+        wn = _f32(w_neigh, "conv_layer params")
+        ws = _f32(w_self, "conv_layer params") if w_self is not None else None
+        b = _f32(bias, "conv_layer params") if bias is not None else None
+        c_src, c_dst = norm
+        agg = torch.empty(n, d_in, dtype=torch.float32, device=x.device)
+        out = torch.empty(n, d_out, dtype=torch.float32, device=x.device)
+        _lib.call("scgib_conv_layer_fwd", _p(x), _p(graph.rowptr), _p(graph.col), _p(c_src),
+                  _p(c_dst), n, d_in, d_out, _p(wn), _p(ws), int(gcn), _p(b), int(relu), _p(agg),
+                  _p(out), _p(graph.dims), _stream())
+        ctx.save_for_backward(x, agg, out if (relu and not premasked) else None, wn, ws, c_src,
+                              c_dst)
+        ctx.graph, ctx.gcn, ctx.mask_in, ctx.has_bias = graph, gcn, mask_in, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, agg, out, wn, ws, c_src, c_dst = ctx.saved_tensors
+        g = _f32(g, "conv_layer.backward")
+        n, d_in = x.shape
+        d_out = g.shape[1]
+        gr = ctx.graph
+        nw = d_in * d_out
+        width = int(_lib.query("scgib_conv_slab_width", d_in, d_out, int(ws is not None)))
+        wg = torch.zeros(width, dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        if n:
+            n_slabs = int(_lib.query("scgib_conv_slabs", n))
+            slab = torch.empty(n_slabs * width, dtype=torch.float32, device=x.device)
+            dz = torch.empty_like(g) if out is not None else None
+            st = _stream()
+            _lib.call("scgib_conv_layer_bwd", _p(g), _p(out), _p(agg), _p(x), _p(gr.rowptr_t),
+                      _p(gr.col_t), _p(c_src), _p(c_dst), n, d_in, d_out, _p(wn), _p(ws),
+                      int(ctx.gcn), int(ctx.mask_in), _p(dz), _p(dx), _p(slab), _p(gr.dims), st)
+            _reduce_jobs([_lib.SlabJob(slab.data_ptr(), wg.data_ptr(), width, n_slabs, 0)], st)
+        shape = (d_in, d_out) if ctx.gcn else (d_out, d_in)
+        dwn = wg[:nw].view(shape)
+        dws = wg[nw:2 * nw].view(shape) if ws is not None else None
+        db = wg[width - d_out:] if ctx.has_bias else None
+        return dx, dwn, dws, db, None, None, None, None, None, None
+
+
+def conv_layer(x, graph, w_neigh, w_self, bias, mode, relu, norm=None):
+    """One graph-convolution layer on the fused HIP kernels:
+    out = act(agg Wn + x Ws + b) with agg[v] = c_dst[v] sum_{u->v} c_src[u] x[u].
+    mode 'gcn' (DGL GraphConv, norm='both': w_neigh [in, out], w_self None) or
+    'mean' (DGL SAGEConv: w_neigh = fc_neigh.weight, w_self = fc_self.weight,
+    both [out, in]).  ``norm``: conv_norm(graph, mode) when already computed."""
+    mode = _conv_mode(mode)
+    if norm is None:
+        norm = conv_norm(graph, mode)
+    return _ConvLayer.apply(x, w_neigh, w_self, bias, graph, mode, bool(relu), norm, False, False)
+
+
+def conv_encoder(h, graph, module):
+    """A whole models.GCN / models.GraphSAGE forward: ``module.layer_sequence()``
+    = [(conv, relu), ...] in forward order, conv.conv_params() = (w_neigh,
+    w_self, bias).  The coefficient vectors are computed once and shared by the
+    layers, forward and backward; between two layers the ReLU mask is applied
+    in the later layer's dx kernel, so no dz is materialised."""
+    mode = _conv_mode(module.conv_mode)
+    norm = conv_norm(graph, mode)
+    seq = module.layer_sequence()
+    for i, (conv, relu) in enumerate(seq):
+        w_neigh, w_self, bias = conv.conv_params()
+        mask_in = i > 0 and bool(seq[i - 1][1])
+        premasked = bool(relu) and i + 1 < len(seq)
+        h = _ConvLayer.apply(h, w_neigh, w_self, bias, graph, mode, bool(relu), norm, mask_in,
+                             premasked)
+    return h
