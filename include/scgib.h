@@ -658,6 +658,67 @@ int scgib_bce_fwd(const float *scores, const float *targets, int64_t n, float *l
                   scgib_stream_t stream);
 int scgib_bce_bwd(const float *scores, const float *targets, int64_t n, const float *g_loss,
                   float *d_scores, scgib_stream_t stream);
+
+/* ---- (f)2: wide task heads + NaN-masked task losses (ABI 24) --------------
+ * The multi-label / regression fine-tunes (train_molpcba.py:108,
+ * train_pep_func.py:131, train_molsider.py:109: 128 / 10 / 27 tasks; ToxCast
+ * 617, Tox21 12) and the losses of models.py:522-543 taken through
+ * MetricWrapper(metric, target_nan_mask="ignore-flatten") (MetricWrapper.py:
+ * 64-66, target[~isnan(target)]: a data-dependent shape, hence a device-host
+ * synchronise that no captured step can contain).
+ * scgib_head_wide_fwd / _bwd: scgib_head_fwd / _bwd's formulas (models.py:
+ *   510-520) for 16 < C <= 1024 outputs, K <= 128 and a multiple of 4; any
+ *   other (K, C): SCGIB_EUNSUPPORTED, as are x, w1, w2, hid or dw2 not 16-byte
+ *   aligned.  hid = relu(x W1^T + b1) [n,64] (saved), out = hid W2^T + b2
+ *   [n,C] (sigmoid applied when `sigmoid`); W2 is walked in column tiles of 64
+ *   staged in LDS, spread over the grid's second dimension.  ru: as
+ *   scgib_head_fwd.  n = 0: the forward writes nothing, the backward zeroes
+ *   the weight gradients.
+ *   Backward, one launch: do = d_out * (sigmoid ? out (1 - out) : 1);
+ *   ceil(C / 16) workgroups each own 16 rows of dW2 = do^T hid and db2 =
+ *   sum_r do (every thread sums its outputs in row order); ceil(n / 16)
+ *   workgroups each own 16 rows: dh = (do W2) [hid > 0], dx = dh W1 (written),
+ *   and the partials of dW1 = dh^T x, db1 = sum_r dh into slab row b of
+ *   64 K + 64 floats, which a scgib_slab_reduce_multi launch issued by this
+ *   call sums in a fixed order (n <= 16: written to dw1 / db1 directly, no
+ *   second launch, slab may be NULL).  slab: scgib_head_wide_slab_floats(n, K).
+ * scgib_task_loss_fwd / _bwd: over scores, targets [n] (the flattened [rows,
+ *   C]), with an element kept when !mask_nan or its target is not NaN, m the
+ *   number kept, per kept element (fp32, torch's formulas)
+ *     SCGIB_LOSS_BCE         (t-1) max(log(1-s),-100) - t max(log s,-100)
+ *                              model.loss, models.py:522-523
+ *     SCGIB_LOSS_BCE_LOGITS  max(x,0) - x t + log1p(exp(-|x|))
+ *                              BCEWithLogitsLoss, models.py:536-539
+ *     SCGIB_LOSS_MAE         |s - t|            lossMAE, models.py:541-543
+ *     SCGIB_LOSS_RMSE        (s - t)^2          loss_RMSE, models.py:532-535
+ *   loss = sum / m (RMSE: sqrt(sum / m)), NaN when m = 0 (torch's mean over
+ *   an empty tensor); count = m (int32, device).  The sum is fp64 in a fixed
+ *   order: at most 64 workgroups (a function of n only), each a fixed tree
+ *   over its threads, the last to arrive adds the partials in workgroup
+ *   order.  ws: scgib_task_loss_ws_doubles() doubles; counter: one zeroed
+ *   uint32, left zero.  Backward, from g_loss (device scalar) and the
+ *   forward's loss and count:
+ *     BCE  g (s-t) / max((1-s) s, 1e-12) / m    BCE_LOGITS  g (sigmoid(x)-t) / m
+ *     MAE  g sign(s-t) / m                      RMSE        g (s-t) / (m loss)
+ *   and exactly 0 at elements left out (everywhere when m = 0).  Nothing is
+ *   read back to the host and no shape depends on the data. */
+enum { SCGIB_LOSS_BCE = 0, SCGIB_LOSS_BCE_LOGITS = 1, SCGIB_LOSS_MAE = 2, SCGIB_LOSS_RMSE = 3 };
+int64_t scgib_head_wide_slab_floats(int64_t n_rows, int32_t k_in);
+int scgib_head_wide_fwd(const float *x, int64_t n_rows, int32_t k_in, const float *w1,
+                        const float *b1, const float *w2, const float *b2, int32_t n_out,
+                        int32_t sigmoid, float *hid, float *out, const scgib_running_update *ru,
+                        scgib_stream_t stream);
+int scgib_head_wide_bwd(const float *x, const float *hid, const float *out, const float *d_out,
+                        int64_t n_rows, int32_t k_in, const float *w1, const float *w2,
+                        int32_t n_out, int32_t sigmoid, float *dx, float *dw1, float *db1,
+                        float *dw2, float *db2, float *slab, scgib_stream_t stream);
+int64_t scgib_task_loss_ws_doubles(void);
+int scgib_task_loss_fwd(const float *scores, const float *targets, int64_t n, int32_t kind,
+                        int32_t mask_nan, double *ws, uint32_t *counter, float *loss,
+                        int32_t *count, scgib_stream_t stream);
+int scgib_task_loss_bwd(const float *scores, const float *targets, int64_t n, int32_t kind,
+                        int32_t mask_nan, const float *g_loss, const float *loss,
+                        const int32_t *count, float *d_scores, scgib_stream_t stream);
 /* Backward of scgib_interaction_fwd.  The KL gradient is g_kl [2 n_last, 64],
  * or g_klmean (device scalar, gradient of kl_mean), or neither (both NULL);
  * g_z1 / g_z2 may be NULL (readouts that feed no loss: zero gradient).

@@ -11,6 +11,7 @@ Layout:
   ops.py       autograd Functions over the C-ABI
   models.py    models.py-compatible Mainmodel / Mainmodel_continue /
                Mainmodel_finetuning / GIN / Set2Set
+  metric_wrapper.py  MetricWrapper.py-compatible MetricWrapper (NaN-masked losses on the device)
   metrics.py   ROC-AUC (OGB semantics) and TU accuracy of the fine-tune configs
   optim.py     one-launch device Adam (drop-in for torch.optim.Adam as the scripts use it)
   cache.py     on-disk CSR cache of a molecule dataset (replaces the pts/ pickles)
@@ -22,10 +23,12 @@ Layout:
 import importlib
 
 __all__ = ["graph", "ops", "models", "dgl", "dist", "synth", "metrics", "optim", "cache", "refckpt",
-           "_lib"]
+           "metric_wrapper", "_lib"]
 
 
 def __getattr__(name):
+    if name == "MetricWrapper":
+        return importlib.import_module(f"{__name__}.metric_wrapper").MetricWrapper
     if name in __all__:
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

@@ -30,6 +30,14 @@ SIGNATURES = {
                                       _P, _P, _P, _P]),
     "scgib_bce_fwd": (ctypes.c_int, [_P, _P, _I64, _P, _P]),
     "scgib_bce_bwd": (ctypes.c_int, [_P, _P, _I64, _P, _P, _P]),
+    "scgib_head_wide_slab_floats": (_I64, [_I64, _I32]),
+    "scgib_head_wide_fwd": (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P,
+                                           _P]),
+    "scgib_head_wide_bwd": (ctypes.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _I32, _I32, _P, _P,
+                                           _P, _P, _P, _P, _P]),
+    "scgib_task_loss_ws_doubles": (_I64, []),
+    "scgib_task_loss_fwd": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
+    "scgib_task_loss_bwd": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     "scgib_pool_copy": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P]),
     "scgib_pool_copy2": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P, _I64, _P]),
     "scgib_stream_signal": (ctypes.c_int, [_P, _P]),
@@ -201,7 +209,7 @@ class RunningUpdate(ctypes.Structure):
                 ("num_batches_tracked", ctypes.c_void_p)]
 
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 STATS_STRIDE = 260
 PGRAD_STRIDE = 324
 HIDDEN = 64

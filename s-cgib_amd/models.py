@@ -292,7 +292,9 @@ FUSE_CONTRAST = True
 # core encoder's chain instead of two torch.rand launches on the critical path
 DEVICE_NOISE = True
 # fine-tune head: predict (+ sigmoid) and the BCE loss on csrc/head.hip (four
-# launches per step instead of ~19 torch ones; tests cover both sides)
+# launches per step instead of ~19 torch ones; tests cover both sides); wider
+# heads (C > 16), the MAE / RMSE / BCE-with-logits losses and MetricWrapper's
+# NaN-masked "ignore-flatten" losses on csrc/task_head.hip
 FUSE_HEAD = True
 
 
@@ -883,13 +885,35 @@ class Mainmodel_finetuning(nn.Module):
         return F.cross_entropy(scores.to(torch.float32), targets.squeeze(dim=-1))
 
     def loss_RMSE(self, scores, targets):
+        if _task_loss_ok(scores, targets):
+            return ops.task_loss(scores, targets, "rmse", ignore_nan=False)
         return torch.sqrt(F.mse_loss(scores, targets))
 
     def BCEWithLogitsLoss(self, scores, targets):
+        if _task_loss_ok(scores, targets):
+            return ops.task_loss(scores, targets, "bce_logits", ignore_nan=False)
         return F.binary_cross_entropy_with_logits(scores, targets)
 
     def lossMAE(self, scores, targets):
+        if _task_loss_ok(scores, targets):
+            return ops.task_loss(scores, targets, "mae", ignore_nan=False)
         return F.l1_loss(scores, targets)
+
+
+def _task_loss_ok(scores, targets):
+    """The device losses of csrc/task_head.hip take the place of the plain
+    F.* call: FUSE_HEAD on, fp32 HIP tensors of one shape, not empty."""
+    return (FUSE_HEAD and scores.is_cuda and targets.is_cuda and scores.shape == targets.shape
+            and scores.dtype == targets.dtype == torch.float32 and scores.numel() > 0)
+
+
+# The loss methods whose NaN-masked mean ("ignore-flatten") MetricWrapper runs
+# as one ops.task_loss launch: the method's function carries the kernel's kind
+# (a bound method forwards attribute reads to its function).
+Mainmodel_finetuning.loss.task_loss_kind = "bce"
+Mainmodel_finetuning.BCEWithLogitsLoss.task_loss_kind = "bce_logits"
+Mainmodel_finetuning.lossMAE.task_loss_kind = "mae"
+Mainmodel_finetuning.loss_RMSE.task_loss_kind = "rmse"
 
 
 def freeze_like_reference(model, num_layers=4):

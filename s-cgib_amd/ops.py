@@ -1549,26 +1549,70 @@ class _PredictHead(torch.autograd.Function):
         return dx, dw1, db1, dw2, db2, None
 
 
+class _PredictHeadWide(torch.autograd.Function):
+    """The same head for 16 < C <= 1024 outputs (csrc/task_head.hip): W2 walked
+    in column tiles, one launch forward; one launch backward plus the slab
+    reduce of dW1 / db1 when the batch has more than 16 rows."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, sigmoid):
+        x = _f32(x, "predict head x")
+        w1, b1, w2, b2 = (_f32(t, "predict head params") for t in (w1, b1, w2, b2))
+        n, k = x.shape
+        c = w2.shape[0]
+        hid = torch.empty(n, HIDDEN, dtype=torch.float32, device=x.device)
+        out = torch.empty(n, c, dtype=torch.float32, device=x.device)
+        ru = take_running_update()  # as _PredictHead: rides in this launch
+        _lib.call("scgib_head_wide_fwd", _p(x), n, k, _p(w1), _p(b1), _p(w2), _p(b2), c,
+                  int(sigmoid), _p(hid), _p(out), _byref(ru[0] if ru else None), _stream())
+        ctx.save_for_backward(x, hid, out, w1, w2)
+        ctx.sigmoid = bool(sigmoid)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, hid, out, w1, w2 = ctx.saved_tensors
+        g = _f32(g, "predict head grad")
+        n, k = x.shape
+        c = w2.shape[0]
+        dx, dw1, dw2 = torch.empty_like(x), torch.empty_like(w1), torch.empty_like(w2)
+        db1 = torch.empty(HIDDEN, dtype=torch.float32, device=x.device)
+        db2 = torch.empty(c, dtype=torch.float32, device=x.device)
+        nslab = int(_lib.query("scgib_head_wide_slab_floats", n, k))
+        slab = torch.empty(nslab, dtype=torch.float32, device=x.device) if nslab else None
+        _lib.call("scgib_head_wide_bwd", _p(x), _p(hid), _p(out), _p(g), n, k, _p(w1), _p(w2), c,
+                  int(ctx.sigmoid), _p(dx), _p(dw1), _p(db1), _p(dw2), _p(db2),
+                  _p(slab) if nslab else None, _stream())
+        return dx, dw1, db1, dw2, db2, None
+
+
+HEAD_C_NARROW = 16   # csrc/head.hip's kHeadCMax: up to here the narrow kernels
+HEAD_C_MAX = 1024    # csrc/task_head.hip's kWideCMax
+
+
 def predict_head_ok(x, seq):
     """Whether ``seq`` is the fine-tune head the kernels implement:
-    Sequential(Linear(K <= 128, 64), ReLU, Linear(64, C <= 16)) on a [B, K]
-    HIP tensor, K a multiple of 4."""
+    Sequential(Linear(K <= 128, 64), ReLU, Linear(64, C <= 1024)) on a [B, K]
+    HIP tensor, K a multiple of 4 (C <= 16: csrc/head.hip, wider:
+    csrc/task_head.hip)."""
     import torch.nn as nn
     return (x.is_cuda and x.dim() == 2 and len(seq) == 3 and isinstance(seq[0], nn.Linear)
             and isinstance(seq[1], nn.ReLU) and isinstance(seq[2], nn.Linear)
             and seq[0].bias is not None and seq[2].bias is not None
             and seq[0].out_features == HIDDEN and seq[2].in_features == HIDDEN
             and x.shape[1] == seq[0].in_features and 1 <= x.shape[1] <= 128
-            and x.shape[1] % 4 == 0 and 1 <= seq[2].out_features <= 16)
+            and x.shape[1] % 4 == 0 and 1 <= seq[2].out_features <= HEAD_C_MAX)
 
 
 def predict_head(x, seq, sigmoid):
     """``sigmoid(seq(x))`` (or ``seq(x)``) for the fine-tune head
     Sequential(Linear, ReLU, Linear) (models.py:510-520: predict, then the
     sigmoid unless the dataset is a regression one) in one launch forward
-    and one backward (scgib_head_fwd / _bwd) instead of ~12 torch launches."""
-    return _PredictHead.apply(x, seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias,
-                              bool(sigmoid))
+    and one backward (scgib_head_fwd / _bwd) instead of ~12 torch launches;
+    more than 16 outputs (the multi-label datasets) run scgib_head_wide_fwd /
+    _bwd.  A shape neither implements raises."""
+    fn = _PredictHead if seq[2].out_features <= HEAD_C_NARROW else _PredictHeadWide
+    return fn.apply(x, seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias, bool(sigmoid))
 
 
 class _BceMean(torch.autograd.Function):
@@ -1596,6 +1640,59 @@ def bce_mean(scores, targets):
     if scores.shape != targets.shape:
         raise _lib.ScgibError(f"bce: scores {tuple(scores.shape)} vs targets {tuple(targets.shape)}")
     return _BceMean.apply(scores, targets)
+
+
+# the masked mean losses of csrc/task_head.hip (SCGIB_LOSS_* in include/scgib.h)
+TASK_LOSS_KINDS = {"bce": 0, "bce_logits": 1, "mae": 2, "rmse": 3}
+
+
+class _TaskLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, t, kind, ignore_nan):
+        s, t = _f32(s, "task loss scores"), _f32(t, "task loss targets")
+        dev = s.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        count = torch.empty((), dtype=torch.int32, device=dev)
+        ws = torch.empty(int(_lib.query("scgib_task_loss_ws_doubles")), dtype=torch.float64,
+                         device=dev)
+        _lib.call("scgib_task_loss_fwd", _p(s), _p(t), s.numel(), kind, int(ignore_nan), _p(ws),
+                  _p(counters(dev, "task_loss", 1)), _p(loss), _p(count), _stream())
+        ctx.save_for_backward(s, t, loss, count)
+        ctx.kind, ctx.ignore_nan = kind, bool(ignore_nan)
+        ctx.mark_non_differentiable(count)
+        return loss, count
+
+    @staticmethod
+    def backward(ctx, g, _g_count):
+        s, t, loss, count = ctx.saved_tensors
+        ds = torch.empty_like(s)
+        _lib.call("scgib_task_loss_bwd", _p(s), _p(t), s.numel(), ctx.kind, int(ctx.ignore_nan),
+                  _p(_f32(g.reshape(1), "task loss grad")), _p(loss), _p(count), _p(ds), _stream())
+        return ds, None, None, None
+
+
+def task_loss(scores, targets, kind, ignore_nan=True, return_count=False):
+    """Mean loss over the elements of ``scores`` / ``targets`` (same shape,
+    fp32) whose target is not NaN — ``metric(scores[~nan], targets[~nan])`` of
+    MetricWrapper's "ignore-flatten" mode (MetricWrapper.py:64-66) without the
+    boolean index: one launch each way, the kept count stays on the device,
+    nothing synchronises, so the step captures.  ``kind``: "bce"
+    (F.binary_cross_entropy), "bce_logits", "mae" (F.l1_loss) or "rmse"
+    (sqrt(F.mse_loss)).  No element kept: the loss is NaN and the gradient
+    zero; masked elements get exactly zero gradient.  ``ignore_nan=False``
+    keeps every element (torch's plain losses, NaN targets propagate).
+    ``return_count``: also the int32 device scalar of kept elements.  The
+    first call per device and stream must be outside graph capture
+    (``counters``)."""
+    if kind not in TASK_LOSS_KINDS:
+        raise _lib.ScgibError(f"task_loss: kind {kind!r} not in {sorted(TASK_LOSS_KINDS)}")
+    if scores.shape != targets.shape:
+        raise _lib.ScgibError(f"task_loss: scores {tuple(scores.shape)} vs targets "
+                              f"{tuple(targets.shape)}")
+    if scores.numel() == 0:
+        raise _lib.ScgibError("task_loss: empty scores")
+    loss, count = _TaskLoss.apply(scores, targets, TASK_LOSS_KINDS[kind], bool(ignore_nan))
+    return (loss, count) if return_count else loss
 
 
 # ---------------------------------------------------------------------------
