@@ -208,6 +208,97 @@ int scgib_conv_layer_bwd(const float *dout, const float *out, const float *agg, 
                          int32_t mask_x, float *dz, float *dx, float *slab, const int32_t *dims,
                          scgib_stream_t stream);
 
+/* ---- Graph Transformer encoder: one GraphTransformerLayer ------------------
+ * (Entry points added to ABI 24: nothing existing changes, so the version that
+ * _lib.py and tests/test_task_loss_cpu.py pin stays 24.)
+ * Replaces MultiHeadAttentionLayer + GraphTransformerLayer of the reference's
+ * Transformer encoder (models.py:832-918, util functions :986-1005) and their
+ * autograd backward.  DGL's apply_edges / send_and_recv are restated, not
+ * linked.  Width 64; heads in {1, 2, 4, 8, 16} (d_h = 64 / heads), anything
+ * else SCGIB_EUNSUPPORTED.  All weights are nn.Linear's [out][in].
+ *
+ *   Q, K, V = h Wq^T + bq, ...
+ *   e(u->v, a) = K[u,a,:] . Q[v,a,:] / sqrt(d_h),  s = exp(clamp(e, -5, 5))
+ *   z[v,a] = sum_{u->v} s,  attn[v,a,:] = sum_{u->v} s V[u,a,:] / (z[v,a] + 1e-6)
+ *   h1  = LN1(h + attn Wo^T + bo)              (eps 1e-5, biased variance, affine)
+ *   r'  = dropout_0.5(relu(h1 W1^T + b1))      (kept entries x 2; eval: no dropout)
+ *   out = LN2(h1 + r' W2^T + b2)
+ *
+ * Forward, five launches:
+ * scgib_gt_qkv_fwd: q, k, v [n][64] from one read of each 64-row tile of h.
+ * scgib_gt_attn_fwd: walks the in-edges of every destination in dst-major CSR
+ *   order (fp32 running sums); writes attn [n][64] and z [n][heads].  score
+ *   (may be NULL; tests) receives the scaled pre-clamp e, [n_edges][heads] in
+ *   CSR edge order.  Scores are otherwise not stored.
+ * scgib_gt_out_fwd: out = LN(h + attn Wo^T + bo); saves the pre-norm rows
+ *   pre [n][64] and stats [n][2] = (mean, rstd).
+ * scgib_gt_ffn_fwd (two launches): r [n][128] = r' above, bits [n][4] = the
+ *   128-bit keep-and-positive mask of each row (bit c of word c / 32), then
+ *   out = LN(h1 + r W2^T + b2) with pre / stats as above.  training != 0:
+ *   the keep bits of row i are the Philox4x32-10 block of counter
+ *   (i, tag, rng[1]) keyed by rng[0] (rng: uint64 {seed, offset}, a state of
+ *   its own, never the compression noise's); the launch's last workgroup
+ *   advances rng[1] (counter: one zeroed uint32, left zero).  drop_mask
+ *   (bytes [n][128], non-zero = keep) replaces the draw; nothing advances.
+ *   pos_bits / keep_bits (may be NULL; tests): the > 0 decisions and the keep
+ *   mask used, same packing.
+ *
+ * Backward, six launches and one slab reduce; no float atomics:
+ * scgib_gt_ffn_bwd (two launches): LayerNorm backward of dout from
+ *   (pre, stats, gamma) -> dp [n][64] (also the residual's gradient);
+ *   dr [n][128] = (dp W2) masked by bits (x 2 when training); dh1 = dp + dr W1.
+ *   slab2: scgib_gt_slab_width(0) floats per workgroup = dW2 [64][128] | db2
+ *   [64] | dgamma [64] | dbeta [64]; slab1: width(1) = dW1 [128][64] | db1 [128].
+ * scgib_gt_out_bwd: LayerNorm backward of dh1 -> dp; dattn = dp Wo;
+ *   slab: width(2) = dWo [64][64] | dbo [64] | dgamma [64] | dbeta [64].
+ * scgib_gt_attn_bwd (two launches): over destinations
+ *     g[v] = dattn[v] / (z[v] + 1e-6),  dzs[v,a] = -sum_d dattn attn / (z + 1e-6),
+ *     dq[v] = sum_{u->v} de K[u],  de = (g[v,a,:] . V[u,a,:] + dzs[v,a]) s [|e| <= 5] / sqrt(d_h)
+ *   then over sources on the transposed CSR
+ *     dk[u] = sum_{u->v} de Q[v],  dv[u] = sum_{u->v} s g[v];
+ *   e and s are recomputed from q and k by the forward's own expression.
+ *   g [n][64] and dzs [n][heads] are workspace the second launch reads.
+ * scgib_gt_qkv_bwd: dh = add + dq Wq + dk Wk + dv Wv (add may be NULL: the
+ *   residual's gradient); slab: width(3) = dWq | dWk | dWv [64][64] each |
+ *   dbq | dbk | dbv.
+ * Every slab kernel runs scgib_gt_slabs(n) workgroups; the caller sums the
+ * slabs with scgib_slab_reduce_multi (fixed order).
+ * Capacity mode: rows >= dims[0] of every output are zeros and add nothing
+ * to the slabs. */
+int64_t scgib_gt_slabs(int64_t n_nodes);
+int64_t scgib_gt_slab_width(int32_t which);
+int scgib_gt_qkv_fwd(const float *h, const float *wq, const float *bq, const float *wk,
+                     const float *bk, const float *wv, const float *bv, int64_t n_nodes, float *q,
+                     float *k, float *v, const int32_t *dims, scgib_stream_t stream);
+int scgib_gt_attn_fwd(const float *q, const float *k, const float *v, const int32_t *rowptr,
+                      const int32_t *col, int64_t n_nodes, int32_t heads, float *attn, float *z,
+                      float *score, const int32_t *dims, scgib_stream_t stream);
+int scgib_gt_attn_bwd(const float *dattn, const float *attn, const float *z, const float *q,
+                      const float *k, const float *v, const int32_t *rowptr, const int32_t *col,
+                      const int32_t *rowptr_t, const int32_t *col_t, int64_t n_nodes,
+                      int32_t heads, float *g, float *dzs, float *dq, float *dk, float *dv,
+                      const int32_t *dims, scgib_stream_t stream);
+int scgib_gt_out_fwd(const float *attn, const float *h, const float *wo, const float *bo,
+                     const float *gamma, const float *beta, int64_t n_nodes, float *pre,
+                     float *stats, float *out, const int32_t *dims, scgib_stream_t stream);
+int scgib_gt_ffn_fwd(const float *h1, const float *w1, const float *b1, const float *w2,
+                     const float *b2, const float *gamma, const float *beta, int64_t n_nodes,
+                     int32_t training, uint64_t *rng, uint32_t *counter, const uint8_t *drop_mask,
+                     float *r, uint32_t *bits, uint32_t *pos_bits, uint32_t *keep_bits, float *pre,
+                     float *stats, float *out, const int32_t *dims, scgib_stream_t stream);
+int scgib_gt_ffn_bwd(const float *dout, const float *pre, const float *stats, const float *gamma,
+                     const float *r, const uint32_t *bits, int32_t training, const float *h1,
+                     const float *w1, const float *w2, int64_t n_nodes, float *dp, float *dr,
+                     float *dh1, float *slab2, float *slab1, const int32_t *dims,
+                     scgib_stream_t stream);
+int scgib_gt_out_bwd(const float *dh1, const float *pre, const float *stats, const float *gamma,
+                     const float *attn, const float *wo, int64_t n_nodes, float *dp, float *dattn,
+                     float *slab, const int32_t *dims, scgib_stream_t stream);
+int scgib_gt_qkv_bwd(const float *dq, const float *dk, const float *dv, const float *h,
+                     const float *wq, const float *wk, const float *wv, const float *add,
+                     int64_t n_nodes, float *dh, float *slab, const int32_t *dims,
+                     scgib_stream_t stream);
+
 /* ---- A5 fused: one GIN layer = GINConv(MLP) + BatchNorm1d + ReLU -----------
  * Replaces, per layer, DGL GINConv + nn.Linear x2 + ReLU + nn.BatchNorm1d +
  * F.relu of GIN.forward (models.py:63-71) and their autograd backward.

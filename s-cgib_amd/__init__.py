@@ -10,7 +10,9 @@ Layout:
   graph.py     DGL-duck-typed graph batch (CSR int32, dst-major) + ingest
   ops.py       autograd Functions over the C-ABI
   models.py    models.py-compatible Mainmodel / Mainmodel_continue /
-               Mainmodel_finetuning / GIN / Set2Set
+               Mainmodel_finetuning / GIN / GCN / GraphSAGE / Transformer / Set2Set
+               (Transformer, GraphTransformerLayer and MultiHeadAttentionLayer are
+               also attributes of the package)
   metric_wrapper.py  MetricWrapper.py-compatible MetricWrapper (NaN-masked losses on the device)
   metrics.py   ROC-AUC (OGB semantics) and TU accuracy of the fine-tune configs
   optim.py     one-launch device Adam (drop-in for torch.optim.Adam as the scripts use it)
@@ -26,9 +28,14 @@ __all__ = ["graph", "ops", "models", "dgl", "dist", "synth", "metrics", "optim",
            "metric_wrapper", "_lib"]
 
 
+_MODEL_NAMES = ("Transformer", "GraphTransformerLayer", "MultiHeadAttentionLayer")
+
+
 def __getattr__(name):
     if name == "MetricWrapper":
         return importlib.import_module(f"{__name__}.metric_wrapper").MetricWrapper
+    if name in _MODEL_NAMES:
+        return getattr(importlib.import_module(f"{__name__}.models"), name)
     if name in __all__:
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

@@ -57,6 +57,19 @@ SIGNATURES = {
                                             _I32, _P, _P, _P, _P]),
     "scgib_conv_layer_bwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P,
                                             _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "scgib_gt_slabs": (_I64, [_I64]),
+    "scgib_gt_slab_width": (_I64, [_I32]),
+    "scgib_gt_qkv_fwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "scgib_gt_attn_fwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P]),
+    "scgib_gt_attn_bwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P,
+                                         _P, _P, _P, _P, _P, _P]),
+    "scgib_gt_out_fwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "scgib_gt_ffn_fwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P,
+                                        _P, _P, _P, _P, _P, _P, _P]),
+    "scgib_gt_ffn_bwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _I64, _P, _P, _P,
+                                        _P, _P, _P, _P]),
+    "scgib_gt_out_bwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "scgib_gt_qkv_bwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "scgib_segment_sum": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     "scgib_segment_broadcast": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I64, _P, _P]),
     "scgib_egonet_workspace_bytes": (_I64, [_I64]),

@@ -7,6 +7,8 @@ constructor/forward signatures and the same ``state_dict`` keys:
   GIN ................ models.py:52-72   (GINConv sum aggregation -> HIP kernel)
   GCN, GraphSAGE ..... models.py:75-104  (GraphConv / SAGEConv layers -> the
                                           fused HIP layer of conv_layer.hip)
+  Transformer ........ models.py:807-918 (per-edge attention + FFN layers ->
+                                          the HIP kernels of gt_layer.hip)
   Mainmodel .......... models.py:546-782 (forward :662-700,
                                           extract_features :702-750)
   Mainmodel_continue . models.py:1010-1276 (the wrapper exp_pretraining.py
@@ -32,8 +34,12 @@ Differences from the reference, all deliberate:
     deferred-reduce machinery), "GCN" and "GraphSAGE" (each layer one fused
     HIP launch forward and two backward, run through the plain two-stream
     encoder branch; DGL 1.1.0's GraphConv / SAGEConv semantics restated, not
-    linked) in Mainmodel and Mainmodel_continue; "Transformer" raises, and
-    the fine-tune / domain-adaptation heads take "GIN" only.
+    linked) in Mainmodel and Mainmodel_continue; the fine-tune /
+    domain-adaptation heads take "GIN" only.  Transformer /
+    GraphTransformerLayer / MultiHeadAttentionLayer (models.py:807-918, on the
+    kernels of gt_layer.hip) are available as modules with the reference's
+    constructor arguments and state_dict keys, but not yet selectable by
+    ``encoder=``: "Transformer" as a string still raises.
 """
 from __future__ import annotations
 
@@ -227,6 +233,100 @@ class GraphSAGE(nn.Module):
 
     def forward(self, g, in_feat):
         return ops.conv_encoder(in_feat, g, self)
+
+
+class MultiHeadAttentionLayer(nn.Module):
+    """Per-edge multi-head attention (models.py:874-918): ``out_dim`` is the
+    width of ONE head.  q_proj / k_proj / v_proj are built as in the reference
+    (their keys are in the state_dict) and never used."""
+
+    def __init__(self, in_dim, out_dim, num_heads):
+        super().__init__()
+        if num_heads <= 0 or in_dim % num_heads != 0:
+            raise ValueError(f"MultiHeadAttentionLayer: width {in_dim} is not a multiple of "
+                             f"num_heads {num_heads}")
+        self.out_dim = out_dim
+        self.num_heads = num_heads
+        self.Q = nn.Linear(in_dim, out_dim * num_heads, bias=True)
+        self.K = nn.Linear(in_dim, out_dim * num_heads, bias=True)
+        self.V = nn.Linear(in_dim, out_dim * num_heads, bias=True)
+        self.hidden_size = in_dim
+        self.head_dim = out_dim // num_heads
+        self.scaling = self.head_dim ** -0.5 if self.head_dim else 0.0  # (unused, as in the reference)
+        self.q_proj = nn.Linear(in_dim, in_dim)
+        self.k_proj = nn.Linear(in_dim, in_dim)
+        self.v_proj = nn.Linear(in_dim, in_dim)
+
+    def forward(self, h, g):
+        """[N, num_heads, out_dim].  Stand-alone use only (the projections are
+        torch linears here); GraphTransformerLayer runs the whole layer,
+        projections included, through ops.gt_layer."""
+        attn = ops.graph_attention(self.Q(h), self.K(h), self.V(h), g, self.num_heads)
+        return attn.view(-1, self.num_heads, self.out_dim)
+
+
+class GraphTransformerLayer(nn.Module):
+    """Graph Transformer layer (models.py:832-871): attention, O, residual +
+    LayerNorm, FFN (H -> 2H -> H, dropout 0.5), residual + LayerNorm, on the
+    HIP kernels of gt_layer.hip.  batchnorm1 / batchnorm2 are built and never
+    used: no gradient, running statistics never move."""
+
+    def __init__(self, in_dim, out_dim, num_heads):
+        super().__init__()
+        if num_heads <= 0 or out_dim % num_heads != 0:
+            raise ValueError(f"GraphTransformerLayer: width {out_dim} is not a multiple of "
+                             f"num_heads {num_heads}")
+        self.in_channels = in_dim
+        self.out_channels = out_dim
+        self.num_heads = num_heads
+        self.attention = MultiHeadAttentionLayer(in_dim, out_dim // num_heads, num_heads)
+        self.O = nn.Linear(out_dim, out_dim)
+        self.batchnorm1 = nn.BatchNorm1d(out_dim)
+        self.batchnorm2 = nn.BatchNorm1d(out_dim)
+        self.layer_norm1 = nn.LayerNorm(out_dim)
+        self.layer_norm2 = nn.LayerNorm(out_dim)
+        self.FFN_layer1 = nn.Linear(out_dim, out_dim * 2)
+        self.FFN_layer2 = nn.Linear(out_dim * 2, out_dim)
+
+    def gt_params(self):
+        """The 16 tensors the layer uses, in ops._GtLayer's order."""
+        a = self.attention
+        return (a.Q.weight, a.Q.bias, a.K.weight, a.K.bias, a.V.weight, a.V.bias,
+                self.O.weight, self.O.bias, self.layer_norm1.weight, self.layer_norm1.bias,
+                self.FFN_layer1.weight, self.FFN_layer1.bias, self.FFN_layer2.weight,
+                self.FFN_layer2.bias, self.layer_norm2.weight, self.layer_norm2.bias)
+
+    def forward(self, h, g, drop_mask=None):
+        return ops.gt_layer(h, g, self, drop_mask)
+
+
+class Transformer(nn.Module):
+    """Transformer encoder (models.py:807-829): embedding_h (no bias) and
+    num_layers + 1 GraphTransformerLayers — the reference appends one extra.
+    ``drop_masks``: one explicit dropout mask (bool [N, 2H], True = keep) per
+    layer instead of the device draw, for parity with a recorded run."""
+
+    fused = False  # not the fused GIN machinery (the fold gate of _encode_forked)
+
+    def __init__(self, in_dim, hidden_dim, num_layers, num_heads, device):
+        super().__init__()
+        if num_heads <= 0 or hidden_dim % num_heads != 0:
+            raise ValueError(f"Transformer: hidden_dim {hidden_dim} is not a multiple of "
+                             f"num_heads {num_heads}")
+        self.h = None
+        self.embedding_h = nn.Linear(in_dim, hidden_dim, bias=False)
+        self.in_dim = in_dim
+        self.hidden_dim = hidden_dim
+        self.device = device
+        self.layers = nn.ModuleList(
+            [GraphTransformerLayer(hidden_dim, hidden_dim, num_heads) for _ in range(num_layers)])
+        self.layers.append(GraphTransformerLayer(hidden_dim, hidden_dim, num_heads))
+
+    def extract_features(self, g, h, drop_masks=None):
+        return ops.gt_encoder(h, g, self, drop_masks)
+
+    def forward(self, g, h, drop_masks=None):
+        return self.extract_features(g, h, drop_masks)
 
 
 ENCODERS = ("GIN", "GCN", "GraphSAGE")

@@ -2486,3 +2486,234 @@ def conv_encoder(h, graph, module):
         h = _ConvLayer.apply(h, w_neigh, w_self, bias, graph, mode, bool(relu), norm, mask_in,
                              premasked)
     return h
+
+
+# ---------------------------------------------------------------------------
+# Transformer encoder: the graph Transformer layer (csrc/gt_layer.hip; the
+# reference's MultiHeadAttentionLayer / GraphTransformerLayer, DGL's edge
+# functions restated)
+# ---------------------------------------------------------------------------
+GT_HEADS = (1, 2, 4, 8, 16)
+GT_FFN = 2 * HIDDEN
+
+# Dropout of the FFN: {seed, offset} (int64) per device, a state of its own —
+# the compression noise state gives exactly one draw per step
+# (NoisePrefetch).  The FFN kernel advances the offset itself, so every launch
+# and every graph replay draws a fresh mask.  One state per device: launches
+# that draw on two streams at once take their offsets in the order they run.
+_DROPOUT_STATES = {}  # device index -> int64 [seed, offset]
+
+
+def dropout_state(device):
+    """The device's dropout state; created on first use with a seed drawn from
+    torch's default CPU generator.  Create it outside graph capture."""
+    idx = torch.device(device).index or 0
+    st = _DROPOUT_STATES.get(idx)
+    if st is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.ScgibError("device dropout state must be created outside graph capture "
+                                  "(run one eager step or call ops.seed_dropout first)")
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        st = _DROPOUT_STATES[idx] = torch.tensor([seed, 0], dtype=torch.int64, device=device)
+    return st
+
+
+def seed_dropout(device, seed, offset=0):
+    """Reset the device dropout stream (seed, offset) in place."""
+    st = dropout_state(device)
+    st.copy_(torch.tensor([int(seed), int(offset)], dtype=torch.int64))
+    return st
+
+
+def _gt_check(name, x, graph, heads):
+    if not x.is_cuda or not graph.rowptr.is_cuda:
+        raise _lib.ScgibError(f"{name}: tensors and graph must be on the HIP device "
+                              "(no CPU fallback)")
+    if x.dim() != 2 or x.shape[1] != HIDDEN:
+        raise _lib.ScgibError(f"{name}: width {tuple(x.shape)[1:]} (the kernels are built for "
+                              f"{HIDDEN})")
+    if int(heads) not in GT_HEADS:
+        raise _lib.ScgibError(f"{name}: num_heads {heads} (supported: {GT_HEADS})")
+    if x.shape[0] != graph.num_nodes():
+        raise _lib.ScgibError(f"{name}: rows != graph nodes")
+
+
+def _unpack_bits(bits):
+    """int32 [n, 4] row masks -> bool [n, 128] (bit c of word c // 32)."""
+    sh = torch.arange(32, dtype=torch.int32, device=bits.device)
+    return ((bits.unsqueeze(-1) >> sh) & 1).bool().reshape(bits.shape[0], GT_FFN)
+
+
+def _gt_attn_fwd(q, k, v, graph, heads, want_score):
+    n, dev = q.shape[0], q.device
+    attn = torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
+    z = torch.empty(n, heads, dtype=torch.float32, device=dev)
+    score = None
+    if want_score:
+        n_edges = int(graph.col.numel()) if graph.col is not None else 0
+        score = torch.zeros(n_edges, heads, dtype=torch.float32, device=dev)
+    _lib.call("scgib_gt_attn_fwd", _p(q), _p(k), _p(v), _p(graph.rowptr), _p(graph.col), n, heads,
+              _p(attn), _p(z), _p(score), _p(graph.dims), _stream())
+    return attn, z, score
+
+
+def _gt_attn_bwd(g_attn, attn, z, q, k, v, graph, heads):
+    n, dev = q.shape[0], q.device
+    g = torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
+    dzs = torch.empty(n, heads, dtype=torch.float32, device=dev)
+    dq, dk, dv = (torch.empty(n, HIDDEN, dtype=torch.float32, device=dev) for _ in range(3))
+    if n:
+        _lib.call("scgib_gt_attn_bwd", _p(g_attn), _p(attn), _p(z), _p(q), _p(k), _p(v),
+                  _p(graph.rowptr), _p(graph.col), _p(graph.rowptr_t), _p(graph.col_t), n, heads,
+                  _p(g), _p(dzs), _p(dq), _p(dk), _p(dv), _p(graph.dims), _stream())
+    return dq, dk, dv
+
+
+class _GraphAttention(torch.autograd.Function):
+    """attn[v,a,:] = sum_{u->v} s V[u,a,:] / (sum_{u->v} s + 1e-6) with
+    s = exp(clamp(K[u,a,:] . Q[v,a,:] / sqrt(d_h), -5, 5))."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, graph, heads, want_score):
+        q, k, v = (_f32(t, "graph_attention") for t in (q, k, v))
+        attn, z, score = _gt_attn_fwd(q, k, v, graph, heads, want_score)
+        ctx.save_for_backward(q, k, v, attn, z)
+        ctx.graph, ctx.heads = graph, heads
+        if score is None:
+            return attn
+        ctx.mark_non_differentiable(score)
+        return attn, score
+
+    @staticmethod
+    def backward(ctx, g, _g_score=None):
+        q, k, v, attn, z = ctx.saved_tensors
+        dq, dk, dv = _gt_attn_bwd(_f32(g, "graph_attention.backward"), attn, z, q, k, v, ctx.graph,
+                                  ctx.heads)
+        return dq, dk, dv, None, None, None
+
+
+def graph_attention(q, k, v, graph, num_heads, return_score=False):
+    """Per-edge multi-head attention over ``graph`` on the HIP kernels: q, k, v
+    [N, 64] -> attn [N, 64] (heads side by side, d_h = 64 / num_heads).
+    ``return_score``: also the scaled pre-clamp scores [E, num_heads] in the
+    graph's dst-major (CSR) edge order (not differentiable; for tests)."""
+    for t in (q, k, v):
+        _gt_check("graph_attention", t, graph, num_heads)
+    return _GraphAttention.apply(q, k, v, graph, int(num_heads), bool(return_score))
+
+
+_GT_SLABS = 4  # FFN_layer2 + LN2 | FFN_layer1 | O + LN1 | Q, K, V
+
+
+class _GtLayer(torch.autograd.Function):
+    """One GraphTransformerLayer: five launches forward, six and one slab
+    reduce backward.  params: Wq bq Wk bk Wv bv Wo bo g1 be1 W1 b1 W2 b2 g2 be2."""
+
+    @staticmethod
+    def forward(ctx, h, graph, heads, training, drop_mask, aux, *params):
+        h = _f32(h, "gt_layer")
+        n, dev = h.shape[0], h.device
+        P = [_f32(p, "gt_layer params") for p in params]
+        wq, bq, wk, bk, wv, bv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2 = P
+        st = _stream()
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+        q, k, v = new(n, HIDDEN), new(n, HIDDEN), new(n, HIDDEN)
+        _lib.call("scgib_gt_qkv_fwd", _p(h), _p(wq), _p(bq), _p(wk), _p(bk), _p(wv), _p(bv), n,
+                  _p(q), _p(k), _p(v), _p(graph.dims), st)
+        attn, z, score = _gt_attn_fwd(q, k, v, graph, heads, aux is not None)
+        pre1, stats1, h1 = new(n, HIDDEN), new(n, 2), new(n, HIDDEN)
+        _lib.call("scgib_gt_out_fwd", _p(attn), _p(h), _p(wo), _p(bo), _p(g1), _p(be1), n,
+                  _p(pre1), _p(stats1), _p(h1), _p(graph.dims), st)
+        r, bits = new(n, GT_FFN), new(n, 4, dtype=torch.int32)
+        pos = new(n, 4, dtype=torch.int32) if aux is not None else None
+        keep = new(n, 4, dtype=torch.int32) if aux is not None else None
+        pre2, stats2, out = new(n, HIDDEN), new(n, 2), new(n, HIDDEN)
+        draw = training and drop_mask is None
+        rng = dropout_state(dev) if draw else None
+        cnt = counters(dev, "gt_dropout", 1) if draw else None
+        _lib.call("scgib_gt_ffn_fwd", _p(h1), _p(w1), _p(b1), _p(w2), _p(b2), _p(g2), _p(be2), n,
+                  int(training), _p(rng), _p(cnt), _p(drop_mask if training else None), _p(r),
+                  _p(bits), _p(pos), _p(keep), _p(pre2), _p(stats2), _p(out), _p(graph.dims), st)
+        if aux is not None:
+            aux["ffn_pos"], aux["keep"], aux["score"] = _unpack_bits(pos), _unpack_bits(keep), score
+        ctx.save_for_backward(h, q, k, v, attn, z, pre1, stats1, h1, r, bits, pre2, stats2,
+                              wq, wk, wv, wo, g1, w1, w2, g2)
+        ctx.graph, ctx.heads, ctx.training = graph, heads, training
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (h, q, k, v, attn, z, pre1, stats1, h1, r, bits, pre2, stats2,
+         wq, wk, wv, wo, g1, w1, w2, g2) = ctx.saved_tensors
+        g = _f32(g, "gt_layer.backward")
+        gr = ctx.graph
+        n, dev = h.shape[0], h.device
+        widths = [int(_lib.query("scgib_gt_slab_width", i)) for i in range(_GT_SLABS)]
+        woff = [sum(widths[:i]) for i in range(_GT_SLABS + 1)]
+        wg = torch.zeros(woff[-1], dtype=torch.float32, device=dev)
+        dh = torch.empty_like(h)
+        if n:
+            n_slabs = int(_lib.query("scgib_gt_slabs", n))
+            slab = torch.empty(n_slabs * woff[-1], dtype=torch.float32, device=dev)
+            slabs = [slab[n_slabs * woff[i]: n_slabs * woff[i + 1]] for i in range(_GT_SLABS)]
+            st = _stream()
+            new = lambda w: torch.empty(n, w, dtype=torch.float32, device=dev)
+            dp2, dr, dh1 = new(HIDDEN), new(GT_FFN), new(HIDDEN)
+            _lib.call("scgib_gt_ffn_bwd", _p(g), _p(pre2), _p(stats2), _p(g2), _p(r), _p(bits),
+                      int(ctx.training), _p(h1), _p(w1), _p(w2), n, _p(dp2), _p(dr), _p(dh1),
+                      _p(slabs[0]), _p(slabs[1]), _p(gr.dims), st)
+            dp1, dattn = new(HIDDEN), new(HIDDEN)
+            _lib.call("scgib_gt_out_bwd", _p(dh1), _p(pre1), _p(stats1), _p(g1), _p(attn), _p(wo),
+                      n, _p(dp1), _p(dattn), _p(slabs[2]), _p(gr.dims), st)
+            dq, dk, dv = _gt_attn_bwd(dattn, attn, z, q, k, v, gr, ctx.heads)
+            _lib.call("scgib_gt_qkv_bwd", _p(dq), _p(dk), _p(dv), _p(h), _p(wq), _p(wk), _p(wv),
+                      _p(dp1), n, _p(dh), _p(slabs[3]), _p(gr.dims), st)
+            _reduce_jobs([_lib.SlabJob(slabs[i].data_ptr(), wg[woff[i]:].data_ptr(), widths[i],
+                                       n_slabs, 0) for i in range(_GT_SLABS)], st)
+        H, F2 = HIDDEN, GT_FFN
+        s0, s1, s2, s3 = (wg[woff[i]: woff[i + 1]] for i in range(_GT_SLABS))
+        dw2, db2, dg2, dbe2 = s0[:H * F2].view(H, F2), s0[H * F2: H * F2 + H], \
+            s0[H * F2 + H: H * F2 + 2 * H], s0[H * F2 + 2 * H:]
+        dw1, db1 = s1[:F2 * H].view(F2, H), s1[F2 * H:]
+        dwo, dbo, dg1, dbe1 = s2[:H * H].view(H, H), s2[H * H: H * H + H], \
+            s2[H * H + H: H * H + 2 * H], s2[H * H + 2 * H:]
+        dwq, dwk, dwv = (s3[i * H * H: (i + 1) * H * H].view(H, H) for i in range(3))
+        dbq, dbk, dbv = (s3[3 * H * H + i * H: 3 * H * H + (i + 1) * H] for i in range(3))
+        return (dh, None, None, None, None, None, dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo, dg1, dbe1,
+                dw1, db1, dw2, db2, dg2, dbe2)
+
+
+def gt_layer(h, graph, layer, drop_mask=None, return_aux=False):
+    """One models.GraphTransformerLayer on the HIP kernels: ``layer.gt_params()``
+    are its 16 used tensors, ``layer.num_heads`` its heads, ``layer.training``
+    decides dropout.  ``drop_mask`` (bool [N, 128], True = keep) replaces the
+    device draw in training.  ``return_aux``: also a dict with the kernels' own
+    decisions — "ffn_pos" / "keep" (bool [N, 128]) and "score" ([E, heads], the
+    scaled pre-clamp scores in dst-major edge order)."""
+    heads = int(layer.num_heads)
+    _gt_check("gt_layer", h, graph, heads)
+    training = bool(layer.training)
+    if drop_mask is not None:
+        if (not drop_mask.is_cuda or drop_mask.dtype != torch.bool
+                or tuple(drop_mask.shape) != (h.shape[0], GT_FFN)):
+            raise _lib.ScgibError(f"gt_layer: drop_mask must be a bool [{h.shape[0]}, {GT_FFN}] "
+                                  "tensor on the HIP device")
+        drop_mask = drop_mask.contiguous()
+    aux = {} if return_aux else None
+    out = _GtLayer.apply(h, graph, heads, training, drop_mask, aux, *layer.gt_params())
+    return (out, aux) if return_aux else out
+
+
+def gt_encoder(h, graph, module, drop_masks=None):
+    """A whole models.Transformer forward: embedding_h (one torch F.linear,
+    [N, in_dim] x [in_dim, 64]) and then every layer through gt_layer's own
+    autograd op.  ``drop_masks``: one mask per layer (see gt_layer)."""
+    if not h.is_cuda:
+        raise _lib.ScgibError(f"gt_encoder: tensor is on {h.device}; the S-CGIB ops run on the "
+                              "HIP device only (no CPU fallback)")
+    if drop_masks is not None and len(drop_masks) != len(module.layers):
+        raise _lib.ScgibError(f"gt_encoder: {len(module.layers)} layers, {len(drop_masks)} masks")
+    h = torch.nn.functional.linear(h.float(), module.embedding_h.weight)
+    for i, layer in enumerate(module.layers):
+        h = gt_layer(h, graph, layer, None if drop_masks is None else drop_masks[i])
+    return h
