@@ -865,6 +865,64 @@ int scgib_recon_logm_bwd(const float *im, const int32_t *graph_ptr, int64_t n_gr
                          const float *S, const int64_t *s_offsets, int32_t kstep,
                          const float *g_loss, float *grad_im, scgib_stream_t stream);
 
+/* ---- A15, on the device: logM targets from the ego-nets, sparse loss -------
+ * (csrc/logm.hip)  L_i[r,c] = max(0, log(A^i[r,c] /
+ * colsum_i[c]) - log(1/n_g)) (util.py:60-91) is zero unless r lies in the
+ * k-hop ball of c, so the targets live on the slots of the k-hop ego batch of
+ * the same graph (scgib_egonet_*: slot j of ball(c) <-> r = ego_nodes[j],
+ * ego_ptr [n_nodes + 1], every ball sorted and holding c).
+ *
+ * scgib_logm_targets: the batch's dst-major CSR (a symmetric graph: the walk
+ *   counts of r -> c and c -> r are taken to be equal), graph_ptr [B + 1],
+ *   kstep = k.  Writes, per slot, s_in = sum_i L_i[r,c] and
+ *   s_sym = sum_i (L_i[r,c] + L_i[c,r]) (fp32; each term formed in fp64 and
+ *   rounded to fp32 as the reference's targets are, then summed in fp64), and
+ *   per molecule C[g] = sum_i ||L_i||_F^2 (fp64, fixed-order sum).  counts:
+ *   scratch of kstep * n_ego uint32 (the walk counts, exact integers).
+ *   Domain: 1 <= kstep <= scgib_logm_max_k() (8; else SCGIB_EUNSUPPORTED),
+ *   molecules of at most scgib_logm_max_graph_nodes() (512) nodes, every walk
+ *   count below 2^31 — which holds whenever (max in-degree)^kstep < 2^31, e.g.
+ *   kstep <= 8 at in-degree <= 12.  Outside it nothing wrong is returned
+ *   silently: bits are set in *err (device int32, zeroed by the caller or
+ *   shared with the ego builder's): 1 an index leaves its molecule or buffer,
+ *   2 a molecule above 512 nodes, 4 a walk count at or above 2^31; the
+ *   affected molecule's targets are then zero or partial and its loss term
+ *   and gradient rows are zero (bits 1, 2).  The reference's quirks are kept:
+ *   log(1/n) uses the molecule's own n; a count of 0, a column without
+ *   in-edges (its NaN) and negative values give 0.
+ * scgib_recon_logm_sparse_fwd: loss = sum_g (k ||G_g||_F^2 - 2 sum_slots s_in
+ *   <x_r, x_c> + C_g) / (k n_g^2), G_g = X_g^T X_g (exact-f32 MFMA), the three
+ *   terms combined in fp64.  gram [B][64*64] is saved for the backward; parts
+ *   holds B * scgib_recon_logm_sparse_parts(max_graph_nodes) doubles;
+ *   loss_graphs [B]; loss a device scalar.  max_graph_nodes (host bound on
+ *   the molecule size) only sizes the grid.
+ * scgib_recon_logm_sparse_bwd: grad_im row c = g_loss (4k (X G)_c - 2 sum_{j
+ *   in ball(c)} s_sym[j] x_{r_j}) / (k n_g^2).
+ * Capacity mode (dims = the batch's device [nodes, edges], n_nodes / n_edges /
+ * n_ego the capacities): live counts are read on the device, a padded molecule
+ * (n = 0) contributes 0, grad rows in [live N, n_nodes) are written as zeros;
+ * nothing is read back. */
+int64_t scgib_logm_max_k(void);
+int64_t scgib_logm_max_graph_nodes(void);
+int scgib_logm_targets(const int32_t *rowptr, const int32_t *col, const int32_t *graph_ptr,
+                       int64_t n_graphs, int64_t n_nodes, int64_t n_edges,
+                       const int32_t *ego_ptr, const int32_t *ego_nodes, int64_t n_ego,
+                       int32_t kstep, uint32_t *counts, float *s_in, float *s_sym, double *C,
+                       int32_t *err, const int32_t *dims, scgib_stream_t stream);
+int64_t scgib_recon_logm_sparse_parts(int64_t max_graph_nodes);
+int scgib_recon_logm_sparse_fwd(const float *im, const int32_t *graph_ptr, int64_t n_graphs,
+                                int64_t n_nodes, const int32_t *ego_ptr,
+                                const int32_t *ego_nodes, int64_t n_ego, const float *s_in,
+                                const double *C, int32_t kstep, int64_t max_graph_nodes,
+                                float *gram, double *parts, float *loss_graphs, float *loss,
+                                const int32_t *dims, scgib_stream_t stream);
+int scgib_recon_logm_sparse_bwd(const float *im, const int32_t *graph_ptr, int64_t n_graphs,
+                                int64_t n_nodes, const int32_t *ego_ptr,
+                                const int32_t *ego_nodes, int64_t n_ego, const float *s_sym,
+                                const float *gram, int32_t kstep, int64_t max_graph_nodes,
+                                const float *g_loss, float *grad_im, const int32_t *dims,
+                                scgib_stream_t stream);
+
 /* ---- A11: contrastive loss (batched_semi_loss, tau = 1) --------------------
  * models.py:606-629 (sim :606-609, semi_loss :611-616, batched :618-629;
  * called at models.py:695 with z1 = sum_nodes(noisy), z2 = graph readout).

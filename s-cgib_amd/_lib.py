@@ -103,6 +103,15 @@ SIGNATURES = {
                                              _P, _P, _P, _P, _I32, _P, _P]),
     "scgib_recon_logm_fwd": (ctypes.c_int, [_P, _P, _I64, _P, _P, _P, _I32, _P, _P, _P]),
     "scgib_recon_logm_bwd": (ctypes.c_int, [_P, _P, _I64, _P, _P, _I32, _P, _P, _P]),
+    "scgib_logm_max_k": (_I64, []),
+    "scgib_logm_max_graph_nodes": (_I64, []),
+    "scgib_logm_targets": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _I32, _P,
+                                          _P, _P, _P, _P, _P, _P]),
+    "scgib_recon_logm_sparse_parts": (_I64, [_I64]),
+    "scgib_recon_logm_sparse_fwd": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _I32,
+                                                   _I64, _P, _P, _P, _P, _P, _P]),
+    "scgib_recon_logm_sparse_bwd": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _I32,
+                                                   _I64, _P, _P, _P, _P]),
     "scgib_contrastive_workspace_floats": (_I64, [_I64]),
     "scgib_contrastive_counters": (_I64, [_I64]),
     "scgib_contrastive_fwd": (ctypes.c_int, [_P, _P, _I64, _P, _P, _P, _P]),

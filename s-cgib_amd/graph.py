@@ -815,3 +815,92 @@ class LogMBatch:
         self.S = torch.cat(S).to(device)
         self.offsets = torch.from_numpy(off).to(device)
         self.C = torch.tensor(C, dtype=torch.float64, device=device)
+
+
+# ---------------------------------------------------------------------------
+# A15 on the device: logM targets on the slots of the step's own ego-nets
+# (csrc/logm.hip)
+# ---------------------------------------------------------------------------
+class LogMSparse:
+    """A batch's logM targets on the slots of its k-hop ego batch (slot j of
+    ball(c) <-> r = ego_nodes[j]): ``s_in`` = S[r, c], ``s_sym`` = S[r, c] +
+    S[c, r] with S = sum_i logM_i (fp32), ``C`` [B] = sum_i ||logM_i||_F^2
+    (fp64), ``kstep`` = k.  ``ego_ptr`` / ``ego_nodes`` are the ego batch's
+    own tensors, ``graph_ptr`` the molecule batch's; ``err`` is the device
+    error word (``error()``; shared with the ego builder's on a StaticBatch
+    graph, where ``StaticBatch.ego_error()`` reads it).  ``dims``: the batch's
+    device sizes in capacity mode, else None."""
+
+    def __init__(self, s_in, s_sym, C, kstep, ego_ptr, ego_nodes, graph_ptr, err=None,
+                 max_graph_nodes=512, dims=None):
+        self.s_in, self.s_sym, self.C = s_in, s_sym, C
+        self.kstep = int(kstep)
+        self.ego_ptr, self.ego_nodes, self.graph_ptr = ego_ptr, ego_nodes, graph_ptr
+        self.err = err
+        self.max_graph_nodes = int(max_graph_nodes)
+        self.dims = dims
+
+    def error(self):
+        """Error bits the target build flagged (0 = none; 1: an index leaves
+        its molecule, 2: a molecule above 512 nodes, 4: a walk count outside
+        the exact domain) — a device read."""
+        return 0 if self.err is None else int(self.err.item())
+
+    def to_dense(self):
+        """Per-molecule dense S = sum_i logM_i ([n, n] fp32 numpy arrays) on
+        the host, zeros outside the balls — for tests and debugging."""
+        gp = self.graph_ptr.cpu().numpy().astype(np.int64)
+        n = int(gp[-1])
+        ep = self.ego_ptr.cpu().numpy().astype(np.int64)[: n + 1]
+        n_s = int(ep[-1]) if n else 0
+        rows = self.ego_nodes.cpu().numpy().astype(np.int64)[:n_s]
+        vals = self.s_in.cpu().numpy()[:n_s]
+        cols = np.repeat(np.arange(n), np.diff(ep))
+        out = []
+        for a, b in zip(gp[:-1], gp[1:]):
+            S = np.zeros((b - a, b - a), np.float32)
+            m = slice(int(ep[a]), int(ep[b]))
+            S[rows[m] - a, cols[m] - a] = vals[m]
+            out.append(S)
+        return out
+
+
+def logm_targets(g: GraphBatch, k: int, ego=None) -> LogMSparse:
+    """The logM targets of ``g`` (util.getM_logM per molecule, k steps) built
+    on ``g``'s HIP device from its k-hop ego batch (scgib_logm_targets); no
+    host work, no n^2 buffer, capturable on a StaticBatch graph.  ``ego``: the
+    ``egonet_batch(g, k)`` of the same graph if the caller already has it."""
+    if g.device.type != "cuda":
+        raise _lib.ScgibError("logm_targets needs the graph on a HIP device (no CPU fallback)")
+    if not g.symmetric:
+        raise _lib.ScgibError("logm_targets expects a symmetric (to_bidirected) graph")
+    k = int(k)
+    kmax = int(_lib.query("scgib_logm_max_k"))
+    if not 1 <= k <= kmax:
+        raise _lib.ScgibError(f"logm_targets: k = {k} outside the supported 1..{kmax}")
+    if ego is None:
+        ego = egonet_batch(g, k)
+    dev = g.device
+    ego_nodes = ego.ndata["_ID"]
+    n_s = int(ego_nodes.shape[0])
+    B, n = g.batch_size, g.num_nodes()
+    if B == 0 or n == 0 or n_s == 0:
+        raise _lib.ScgibError("logm_targets: empty batch")
+    err = getattr(g, "err_buf", None)
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    counts = torch.empty(k * n_s, dtype=torch.int32, device=dev)
+    s_in = torch.empty(n_s, dtype=torch.float32, device=dev)
+    s_sym = torch.empty(n_s, dtype=torch.float32, device=dev)
+    C = torch.empty(B, dtype=torch.float64, device=dev)
+    _lib.call("scgib_logm_targets", _ptr(g.rowptr), _ptr(g.col), _ptr(g.graph_ptr), B, n,
+              g.edge_capacity(), _ptr(ego.graph_ptr), _ptr(ego_nodes), n_s, k, _ptr(counts),
+              _ptr(s_in), _ptr(s_sym), _ptr(C), _ptr(err), _ptr(g.dims), _stream())
+    if g.dims is None:
+        code = int(err.item())
+        if code:
+            raise _lib.ScgibError(f"scgib_logm_targets flagged error bits {code} (1: an index "
+                                  "leaves its molecule, 2: a molecule above 512 nodes, 4: a "
+                                  "walk count outside the exact domain)")
+    return LogMSparse(s_in, s_sym, C, k, ego.graph_ptr, ego_nodes, g.graph_ptr, err,
+                      max(g.max_graph_nodes, 1), g.dims)

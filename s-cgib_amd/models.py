@@ -576,7 +576,8 @@ class _SCGIBCore(nn.Module):
         sub_readout.record_stream(main)
         return ego, (graph_features, subgraphs_features, sub_readout, None, None)
 
-    def _losses(self, batch_g, im, kl_mean, z1, z2, mlp, batch_size, batch_logMs=None):
+    def _losses(self, batch_g, im, kl_mean, z1, z2, mlp, batch_size, batch_logMs=None,
+                ego=None):
         # the contrastive loss needs only the two readouts: on the side stream
         # it (and, through autograd, its backward) overlaps the head MLP and
         # the reconstruction loss, which form the critical path
@@ -607,8 +608,14 @@ class _SCGIBCore(nn.Module):
             rec = ops.recon_adj(im, batch_g)
         elif self.recons_type == "logM":  # models.py:692-693 / 770-782
             if batch_logMs is None:
-                raise ValueError("recons_type='logM' needs batch_logMs (graph.trans_logM per "
-                                 "molecule, or a graph.LogMBatch)")
+                if not im.is_cuda:
+                    raise ValueError("recons_type='logM' needs batch_logMs (graph.trans_logM per "
+                                     "molecule, or a graph.LogMBatch) on CPU tensors")
+                # targets built on the device from the step's own ego batch
+                # (``ego``: the one the encoders ran on, when this step built
+                # it; k_transition is the ball radius and kstep, as in the
+                # reference's exp_tudataset.py)
+                batch_logMs = G.logm_targets(batch_g, self.k_transition, ego)
             rec = ops.recon_logm(im, batch_g, batch_logMs)
         else:  # the reference returns -1.0 (models.py:694-695)
             rec = torch.tensor(-1.0, device=im.device)
@@ -672,16 +679,18 @@ class Mainmodel(_SCGIBCore):
             im, _, _, z2, z1 = self._extract(self, batch_g, None, ego, None, noise, enc)
             self._last_z1 = z1
         else:
+            ego = None
             if flatten_batch_subgraphs is None:
                 flatten_batch_subgraphs, x_subs = self._prepare_ego(batch_g, None, batch_x,
                                                                     x_subs)
+                ego = flatten_batch_subgraphs  # built here on the device: reused by logM
             batch_x = self.transfer_d(batch_x)
             x_subs = self.transfer_d(x_subs)
             im, kl, noisy, z2 = self.extract_features(None, batch_g, batch_x,
                                                       flatten_batch_subgraphs, x_subs, device,
                                                       noise)
         kl_loss, con, rec = self._losses(batch_g, im, self._last_kl_mean, self._last_z1, z2,
-                                         self.MLP, batch_size, batch_logMs)
+                                         self.MLP, batch_size, batch_logMs, ego)
         ops.join_aside()
         _drop_graph_refs(self)
         return None, kl_loss, con, rec
@@ -752,9 +761,11 @@ class Mainmodel_continue(_SCGIBCore):
                                                    enc)
             self.model._last_z1 = z1
         else:
+            ego = None
             if flatten_batch_subgraphs is None:
                 flatten_batch_subgraphs, x_subs = self._prepare_ego(batch_g, None, batch_x,
                                                                     x_subs)
+                ego = flatten_batch_subgraphs  # built here on the device: reused by logM
             batch_x = self.transfer_d(batch_x)
             x_subs = self.transfer_d(x_subs)
             im, kl, noisy, z2 = self.model.extract_features(None, batch_g, batch_x,
@@ -762,7 +773,7 @@ class Mainmodel_continue(_SCGIBCore):
                                                             device, noise)
         kl_loss, con, rec = self._losses(batch_g, im, self.model._last_kl_mean,
                                          self.model._last_z1, z2, self.MLP, batch_size,
-                                         batch_logMs)
+                                         batch_logMs, ego)
         ops.stamp("losses_end")
         ops.join_aside()
         _drop_graph_refs(self, self.model)

@@ -2355,10 +2355,59 @@ class _ReconLogM(torch.autograd.Function):
         return grad, None, None
 
 
+class _ReconLogMSparse(torch.autograd.Function):
+    """loss_recon on device-built targets (graph.LogMSparse): Gram + slot
+    form, csrc/logm.hip; runs in capacity mode and under graph capture."""
+
+    @staticmethod
+    def forward(ctx, im, graph, logm):
+        im = _f32(im, "recon_logm")
+        if im.shape[1] != HIDDEN:
+            raise _lib.ScgibError(f"recon_logm kernels are built for width {HIDDEN}")
+        B, n = graph.batch_size, graph.num_nodes()
+        if (logm.graph_ptr.data_ptr() != graph.graph_ptr.data_ptr() or logm.C.shape[0] != B
+                or logm.ego_ptr.shape[0] != n + 1 or (logm.dims is None) != (graph.dims is None)):
+            raise _lib.ScgibError("logM targets (LogMSparse) were built for another batch")
+        if im.shape[0] != n:
+            raise _lib.ScgibError(f"recon_logm: {im.shape[0]} rows for a batch of {n} nodes")
+        dev = im.device
+        n_s = int(logm.ego_nodes.shape[0])
+        gram = torch.empty(B, HIDDEN * HIDDEN, dtype=torch.float32, device=dev)
+        parts = torch.empty(B * int(_lib.query("scgib_recon_logm_sparse_parts",
+                                               logm.max_graph_nodes)),
+                            dtype=torch.float64, device=dev)
+        lossg = torch.empty(B, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _launch("scgib_recon_logm_sparse_fwd", {"n": n, "B": B, "n_s": n_s}, _p(im),
+                _p(graph.graph_ptr), B, n, _p(logm.ego_ptr), _p(logm.ego_nodes), n_s,
+                _p(logm.s_in), _p(logm.C), logm.kstep, logm.max_graph_nodes, _p(gram), _p(parts),
+                _p(lossg), _p(loss), _p(graph.dims), _stream())
+        ctx.save_for_backward(im, gram)
+        ctx.graph, ctx.logm = graph, logm
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        im, gram = ctx.saved_tensors
+        g = _f32(g, "recon_logm.backward").reshape(1)
+        grad = torch.empty_like(im)
+        gr, lm = ctx.graph, ctx.logm
+        n_s = int(lm.ego_nodes.shape[0])
+        _launch("scgib_recon_logm_sparse_bwd", {"n": im.shape[0], "B": gr.batch_size, "n_s": n_s},
+                _p(im), _p(gr.graph_ptr), gr.batch_size, im.shape[0], _p(lm.ego_ptr),
+                _p(lm.ego_nodes), n_s, _p(lm.s_sym), _p(gram), lm.kstep, lm.max_graph_nodes,
+                _p(g), _p(grad), _p(gr.dims), _stream())
+        return grad, None, None
+
+
 def recon_logm(im, graph, logm):
     """loss_recon (models.py:770-782) on the device.  ``logm`` is a
-    graph.LogMBatch or the reference's list of per-molecule [k, n, n]
-    targets (packed here)."""
+    graph.LogMSparse (device-built targets on the ego batch's slots: the Gram
+    + slot kernels, capacity mode and capture included), or a
+    graph.LogMBatch / the reference's list of per-molecule [k, n, n] targets
+    (packed here; the dense kernels)."""
+    if isinstance(logm, _graph.LogMSparse):
+        return _ReconLogMSparse.apply(im, graph, logm)
     if not isinstance(logm, _graph.LogMBatch):
         logm = _graph.LogMBatch(list(logm), im.device)
     return _ReconLogM.apply(im, graph, logm)
