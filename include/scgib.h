@@ -236,7 +236,8 @@ int scgib_conv_layer_bwd(const float *dout, const float *out, const float *agg, 
  *   128-bit keep-and-positive mask of each row (bit c of word c / 32), then
  *   out = LN(h1 + r W2^T + b2) with pre / stats as above.  training != 0:
  *   the keep bits of row i are the Philox4x32-10 block of counter
- *   (i, tag, rng[1]) keyed by rng[0] (rng: uint64 {seed, offset}, a state of
+ *   (i, tag, rng[1]) with tag = 0x47544c31 (the layouts are written out at
+ *   scgib_noise_uniform) keyed by rng[0] (rng: uint64 {seed, offset}, a state of
  *   its own, never the compression noise's); the launch's last workgroup
  *   advances rng[1] (counter: one zeroed uint32, left zero).  drop_mask
  *   (bytes [n][128], non-zero = keep) replaces the draw; nothing advances.
@@ -699,7 +700,19 @@ int scgib_interaction_fwd(const float *f, const float *t, const float *s,
  * rng_state[0] (seed) and rng_state[1] (offset; uint64, device) -> u_gate
  * [n_rows], u_feat [n_rows][64], passed to scgib_interaction_fwd as noise.
  * The last workgroup advances rng_state[1] by one, so every launch / graph
- * replay draws fresh noise.  counter: one zeroed uint32, left zero. */
+ * replay draws fresh noise.  counter: one zeroed uint32, left zero.
+ *
+ * Counter layouts (Philox4x32-10 as in Random123: counter words c0..c3, key
+ * (k0, k1) = (low, high) half of the seed, off_lo / off_hi the halves of the
+ * offset; a 32-bit word x becomes the uniform (x >> 8) * 2^-24):
+ *   u_gate[r]              = word 0 of the block of counter (r, 16, off_lo, off_hi)
+ *   u_feat[r][4c .. 4c+3]  = the four words of counter (r, c, off_lo, off_hi),
+ *                            c = 0..15, so the gate's word 1 (16) is no quad's
+ *   dropout keep bits of row r (scgib_gt_ffn_fwd, a state of its own) = the
+ *                            four words of (r_lo, tag ^ r_hi, off_lo, off_hi),
+ *                            tag = 0x47544c31; bit c % 32 of word c / 32 keeps
+ *                            column c, words in block order
+ * The draws depend on (row, offset, seed) only, never on the grid. */
 int scgib_noise_uniform(float *u_gate, float *u_feat, int64_t n_rows, uint64_t *rng_state,
                         uint32_t *counter, scgib_stream_t stream);
 

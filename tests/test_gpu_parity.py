@@ -254,10 +254,12 @@ def _interaction_oracle(p, f, s, counts, u_gate, u_feat, bn_state):
     return im, z1, z2, kl
 
 
-@pytest.mark.parametrize("training", [True, False])
-def test_interaction_fwd_bwd(pkg, dev, training):
+def _check_interaction(pkg, dev, training, g, gh, extreme=False):
+    """ops.interaction forward + backward on batch ``g`` against the oracle's
+    per-graph loops.  ``extreme``: rows of the last graph (which must span more
+    than one 32-row chunk) get the gate uniforms 0 and 1 - 2^-24, and a few
+    feature entries likewise, first and later chunks alike."""
     torch.manual_seed(0)
-    g, gh = rand_graph(pkg, 48, "qm9", 6, dev)
     n, B = g.num_nodes(), g.batch_size
     counts = torch.from_numpy(gh.batch_num_nodes_host())
     comp = torch.nn.Sequential(torch.nn.Linear(64, 64), torch.nn.BatchNorm1d(64),
@@ -271,6 +273,16 @@ def test_interaction_fwd_bwd(pkg, dev, training):
     f = torch.randn(n, 64)
     s = torch.randn(n, 64)
     u_gate, u_feat = torch.rand(n), torch.rand(n, 64)
+    n_last = int(counts[-1])
+    if extreme:
+        assert n_last > 64
+        r0, u_max = n - n_last, 1.0 - 2.0 ** -24
+        for r, u in ((1, u_max), (2, 0.0), (32, 0.0), (33, u_max), (64, u_max), (n_last - 1, 0.0)):
+            u_gate[r0 + r] = u
+        for r, c, u in ((0, 0, 0.0), (3, 5, u_max), (40, 3, 0.0), (40, 7, u_max), (n_last - 1, 63, u_max),
+                        (-1, 1, 0.0), (-1, 62, u_max)):  # (row -1: the graph before)
+            u_feat[r0 + r, c] = u
+        assert float(u_gate.max()) == u_max < 1.0 and float(u_gate.min()) == 0.0
     # oracle (CPU)
     p = {"compressor.0.weight": comp[0].weight, "compressor.0.bias": comp[0].bias,
          "compressor.1.weight": comp[1].weight, "compressor.1.bias": comp[1].bias,
@@ -305,6 +317,7 @@ def test_interaction_fwd_bwd(pkg, dev, training):
     for a, b, nm in ((im, im_r, "im"), (z1, z1_r, "z1"), (z2, z2_r, "z2"), (kl, kl_r, "kl"),
                      (kl_mean, kl_r.mean(), "kl_mean")):
         assert rel_err(a.detach().cpu(), b.detach()) < ACT_TOL, nm
+    assert kl.shape == (2 * n_last, 64)
     if training:
         for k in ("running_mean", "running_var"):
             assert rel_err(getattr(comp_d[1], k).cpu(), bn_state["compressor.1." + k]) < 1e-5
@@ -327,6 +340,148 @@ def test_interaction_fwd_bwd(pkg, dev, training):
     cancelled = CANCELLED if training else ("attn_layer.bias",)
     check_grads(grads, lambda k: getattr(mods[k.rsplit(".", 1)[0]], k.rsplit(".", 1)[1]).grad,
                 tol=GRAD_TOL, cancelled=cancelled, metric="l2")
+
+
+@pytest.mark.parametrize("training", [True, False])
+def test_interaction_fwd_bwd(pkg, dev, training):
+    g, gh = rand_graph(pkg, 48, "qm9", 6, dev)
+    _check_interaction(pkg, dev, training, g, gh)
+
+
+def path_batch(pkg, counts, dev):
+    """A batch of path graphs of the given node counts (the interaction
+    kernels read graph_ptr only; the topology does not matter)."""
+    mols = []
+    for n in counts:
+        a = np.arange(n - 1, dtype=np.int64)
+        mols.append((np.stack([a, a + 1]), np.zeros((n, 1), np.float32)))
+    gh, kept = pkg.graph.collate_pyg(mols)
+    assert len(kept) == len(counts) and gh.batch_num_nodes_host().tolist() == list(counts)
+    return gh.to(dev), gh
+
+
+# The kernels walk a graph in 32-row chunks: the first stays in registers,
+# later ones are reloaded, and the last graph's later chunks have their gate
+# recomputed for the KL store.  Every boundary (31 / 32 / 33, 64 / 65, 97 =
+# three chunks and a row) is crossed, and the last graph is in turn small,
+# exactly one chunk, and multi-chunk.
+CHUNK_COUNTS = [[2, 31, 32, 33, 5], [7, 64, 65], [33, 2], [16, 17, 97], [40] * 6 + [32]]
+
+
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("counts", CHUNK_COUNTS, ids=lambda c: "-".join(map(str, c)))
+def test_interaction_fwd_bwd_multi_chunk(pkg, dev, training, counts):
+    g, gh = path_batch(pkg, counts, dev)
+    _check_interaction(pkg, dev, training, g, gh)
+
+
+@pytest.mark.parametrize("training", [True, False])
+def test_interaction_fwd_bwd_extreme_uniforms(pkg, dev, training):
+    """u_gate = 0 and 1 - 2^-24 (where log(1 - e) sits on a 1e-4 difference)
+    and the same extremes of u_feat, on first- and later-chunk rows of a
+    three-chunk last graph, at the unchanged bars."""
+    g, gh = path_batch(pkg, [16, 17, 97], dev)
+    _check_interaction(pkg, dev, training, g, gh, extreme=True)
+
+
+_INT_SENTINEL = -7.0
+_INT_GUARD = 8  # sentinel rows behind every output
+
+
+def _interaction_fwd_raw(pkg, dev, gptr, n_live, n_rows, training, pad, seed=11):
+    """scgib_interaction_fwd through the C ABI on sentinel-filled outputs of
+    ``n_rows`` (+ _INT_GUARD) rows; the inputs' first ``n_live`` rows and the
+    parameters depend on ``seed`` only.  Returns the output buffers."""
+    ops = pkg.ops
+    gen = torch.Generator().manual_seed(seed)
+    rnd = lambda *shape: torch.randn(*shape, generator=gen)  # noqa: E731
+    f, t, s = rnd(n_live, 64), rnd(n_live, 64), rnd(n_live, 64)
+    ug, uf = torch.rand(n_live, generator=gen), torch.rand(n_live, 64, generator=gen)
+    gamma, beta, rm = 1 + 0.2 * rnd(64), 0.2 * rnd(64), rnd(64)
+    rv = 0.5 + torch.rand(64, generator=gen)
+    w2, b2, watt, batt = 0.2 * rnd(64), 0.1 * rnd(1), 0.2 * rnd(128), 0.1 * rnd(1)
+    spare = n_rows - n_live  # capacity rows of the inputs hold live-looking values
+    f, t, s, uf = (torch.cat([x, 3 + torch.rand(spare, 64, generator=gen)]) for x in (f, t, s, uf))
+    ug = torch.cat([ug, torch.rand(spare, generator=gen)])
+    B = len(gptr) - 1
+    n_last = gptr[-1] - gptr[-2]
+    d = lambda x: x.to(dev).contiguous()  # noqa: E731
+    full = lambda *shape: torch.full(shape, _INT_SENTINEL, dtype=torch.float32, device=dev)  # noqa: E731
+    out = {"im": full(n_rows + _INT_GUARD, 128), "lam": full(n_rows + _INT_GUARD),
+           "logit": full(n_rows + _INT_GUARD), "z1": full(B + _INT_GUARD, 64),
+           "z2": full(B + _INT_GUARD, 64), "stats": full(B + _INT_GUARD, ops.STATS_STRIDE),
+           "kl": full(2 * n_last + _INT_GUARD, 64), "kl_mean": full(1 + _INT_GUARD)}
+    ins = [d(x) for x in (f, t, s, ug, uf)]
+    gp = torch.tensor(gptr, dtype=torch.int32, device=dev)
+    par = [d(x) for x in (gamma, beta, rm, rv, w2, b2, watt, batt)]
+    p = ops._p
+    pkg._lib.call("scgib_interaction_fwd", *(p(x) for x in ins), p(gp), B, n_rows, p(par[0]),
+                  p(par[1]), p(par[2]), p(par[3]), 1e-5, int(training), p(par[4]), p(par[5]),
+                  p(par[6]), p(par[7]), p(out["im"]), p(out["z1"]), p(out["z2"]), p(out["lam"]),
+                  p(out["logit"]), p(out["stats"]), p(out["kl"]), p(out["kl_mean"]), int(pad),
+                  ops._stream())
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in out.items()}
+
+
+def _untouched(x):
+    return bool((x == _INT_SENTINEL).all())
+
+
+_STATS_USED = 259  # floats of a graph's stats slab that the forward writes
+
+
+@pytest.mark.parametrize("training", [True, False])
+def test_interaction_fwd_capacity_padding(pkg, dev, training):
+    """pad_rows = 1 with a capacity of N + 70 rows (more than the 64 padding
+    workgroups, so some take two rows): rows [N, N + 70) of im / lam / logit
+    are exactly zero, rows < N and every per-graph output are bitwise the
+    exact-size call's, and nothing behind the capacity is written."""
+    gptr = [0, 16, 33, 130]
+    N, B, cap = gptr[-1], len(gptr) - 1, gptr[-1] + 70
+    exact = _interaction_fwd_raw(pkg, dev, gptr, N, N, training, pad=0)
+    padded = _interaction_fwd_raw(pkg, dev, gptr, N, cap, training, pad=1)
+    for k in ("im", "lam", "logit"):
+        assert torch.equal(padded[k][:N], exact[k][:N]), k
+        assert torch.count_nonzero(padded[k][N:cap]) == 0, k
+        assert _untouched(padded[k][cap:]) and _untouched(exact[k][N:]), k
+        assert not (exact[k][:N] == _INT_SENTINEL).any(), k
+    for k, rows in (("z1", B), ("z2", B), ("kl", 2 * (gptr[-1] - gptr[-2])), ("kl_mean", 1)):
+        assert torch.equal(padded[k], exact[k]), k  # (sentinel rows included)
+        assert _untouched(exact[k][rows:]) and not (exact[k][:rows] == _INT_SENTINEL).any(), k
+    assert torch.equal(padded["stats"][:B, :_STATS_USED], exact["stats"][:B, :_STATS_USED])
+    assert _untouched(padded["stats"][B:])
+
+
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("where", ["middle", "last"])
+def test_interaction_fwd_empty_graph(pkg, dev, training, where):
+    """A graph_ptr with a repeated entry (C ABI only: ops.interaction rejects a
+    graph under 2 rows in training and no collate produces an empty one): the
+    empty graph's z1 / z2 rows are zero, kl_mean is 0 when it is the last, and
+    every other graph's outputs are bitwise those of the batch without it."""
+    base_ptr = [0, 7, 47, 80]  # 7 | 40 (two chunks) | 33 (two chunks)
+    N = base_ptr[-1]
+    base = _interaction_fwd_raw(pkg, dev, base_ptr, N, N, training, pad=0)
+    if where == "middle":
+        gptr, live, empty = [0, 7, 7, 47, 80], [0, 2, 3], 1
+    else:
+        gptr, live, empty = [0, 7, 47, 80, 80], [0, 1, 2], 3
+    got = _interaction_fwd_raw(pkg, dev, gptr, N, N, training, pad=0)
+    for k in ("im", "lam", "logit"):
+        assert torch.equal(got[k], base[k]), k
+        assert not (got[k][:N] == _INT_SENTINEL).any(), k
+    for k in ("z1", "z2"):
+        assert torch.equal(got[k][live], base[k][:3]), k
+        assert torch.count_nonzero(got[k][empty]) == 0, k
+        assert _untouched(got[k][4:]), k
+    assert torch.equal(got["stats"][live, :_STATS_USED], base["stats"][:3, :_STATS_USED])
+    if where == "middle":  # the last graph is still the 33-row one
+        assert torch.equal(got["kl"], base["kl"]) and torch.equal(got["kl_mean"], base["kl_mean"])
+        assert not (got["kl"][:66] == _INT_SENTINEL).any()
+    else:  # an empty last graph: a [0, 64] KL tensor, mean 0
+        assert float(got["kl_mean"][0]) == 0.0 and _untouched(got["kl_mean"][1:])
+        assert _untouched(got["kl"])
 
 
 # ---------------------------------------------------------------------------
