@@ -119,8 +119,10 @@ int scgib_stream_wait(uint32_t *words, uint32_t *fault, uint32_t *host_fault,
  * scgib_graph_split_launch replays lane 0 on `stream` (the creation stream,
  * else SCGIB_EINVAL) and lane 1 on the side stream, with one launch's stream
  * semantics: ordered after earlier work on `stream`, later work on `stream`
- * ordered after both lanes.  scgib_graph_split_destroy waits for the side
- * lane and frees it. */
+ * ordered after both lanes (the side stream waits, through an event recorded
+ * at each launch, for the earlier work on `stream`, however long its queue).
+ * scgib_graph_split_destroy waits for both lanes of the last replay and
+ * frees the split. */
 int scgib_graph_split(void *graph, uint32_t *words, int32_t n_slots, uint32_t *fault,
                       uint32_t *host_fault, scgib_stream_t stream, void **out, int32_t *info);
 int scgib_graph_split_launch(void *split, scgib_stream_t stream);

@@ -20,7 +20,11 @@
 // signal and lane 0 always ends after a wait on lane 1's last node, so a
 // replay is ordered after the caller's earlier work on its stream, the
 // caller's later work after the whole replay, and replay i+1 after replay i
-// in both lanes — the same stream semantics as one graph launch.
+// in both lanes — the same stream semantics as one graph launch.  The waits
+// are bounded (0.2 s, below), so that argument alone holds only while lane 0
+// starts promptly: each launch therefore also orders the side stream after
+// the caller's stream on the host (an event, scgib_graph_split_launch), and
+// lane 1 cannot meet its first wait before the caller's earlier work is done.
 //
 // The two lanes must run on hardware queues the device schedules
 // concurrently.  The side stream is NON-blocking (tools/lane_probe.hip: a
@@ -61,16 +65,32 @@ struct Split {
     hipGraphExec_t exec[2] = {nullptr, nullptr};
     hipStream_t side = nullptr;
     hipStream_t caller = nullptr;
+    // host-side ordering (scgib_graph_split_launch): `start` is recorded on
+    // the caller's stream before the lanes go out and the side stream waits
+    // for it; `done` is recorded behind the last lane 0 by release()
+    hipEvent_t start = nullptr, done = nullptr;
     int32_t info[8] = {};
 };
 
 void release(Split *s) {
+    // both lanes of the last replay: lane 1 on the side stream, and lane 0,
+    // which still runs its tail on the caller's stream after lane 1's last
+    // node.  The event goes behind every lane-0 launch so far; recorded here
+    // and not per replay, where a second marker between two back-to-back
+    // steps cost device time.  (A caller stream that is being
+    // captured can neither take the record nor be waited for.)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (s->done && s->exec[0] && hipStreamIsCapturing(s->caller, &cap) == hipSuccess &&
+        cap == hipStreamCaptureStatusNone && hipEventRecord(s->done, s->caller) == hipSuccess)
+        (void)hipEventSynchronize(s->done);
     if (s->side) (void)hipStreamSynchronize(s->side);
     for (int l = 0; l < 2; ++l) {
         if (s->exec[l]) (void)hipGraphExecDestroy(s->exec[l]);
         if (s->graph[l]) (void)hipGraphDestroy(s->graph[l]);
     }
     if (s->side) (void)hipStreamDestroy(s->side);
+    if (s->start) (void)hipEventDestroy(s->start);
+    if (s->done) (void)hipEventDestroy(s->done);
     delete s;
 }
 
@@ -319,6 +339,9 @@ extern "C" int scgib_graph_split(void *graph, uint32_t *words, int32_t n_slots, 
             return fail(e);
     }
     s->caller = as_stream(stream);
+    if ((e = hipEventCreateWithFlags(&s->start, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming)) != hipSuccess)
+        return fail(e);
     if (s->exec[1]) {
         // a side stream on a queue other than the caller's (header comment)
         std::vector<hipStream_t> shared;
@@ -362,16 +385,25 @@ extern "C" int scgib_graph_split(void *graph, uint32_t *words, int32_t n_slots, 
 }
 
 // One replay: lane 0 on `stream`, lane 1 on the split's own side stream.
+// The side stream is first ordered, on the host, after whatever the caller's
+// stream holds so far (an event record + stream wait, outside both graphs):
+// lane 1's in-graph waits give up after 0.2 s, which orders it after lane 0
+// only while lane 0 starts within that time — not behind a long queue of the
+// caller's earlier work (an eval pass, checkpoint copies).
 extern "C" int scgib_graph_split_launch(void *split, scgib_stream_t stream) {
     if (!split) return SCGIB_EINVAL;
     Split *s = reinterpret_cast<Split *>(split);
     if (as_stream(stream) != s->caller) return SCGIB_EINVAL;  // the queue check was against it
-    hipError_t e = hipGraphLaunch(s->exec[0], as_stream(stream));
+    hipError_t e = hipSuccess;
+    if (s->exec[1] && ((e = hipEventRecord(s->start, s->caller)) != hipSuccess ||
+                       (e = hipStreamWaitEvent(s->side, s->start, 0)) != hipSuccess))
+        return static_cast<int>(e);
+    e = hipGraphLaunch(s->exec[0], s->caller);
     if (e == hipSuccess && s->exec[1]) e = hipGraphLaunch(s->exec[1], s->side);
     return e == hipSuccess ? SCGIB_OK : static_cast<int>(e);
 }
 
-// Waits for the side lane's last replay, then frees both graphs and the stream.
+// Waits for both lanes' last replay, then frees both graphs and the stream.
 extern "C" int scgib_graph_split_destroy(void *split) {
     if (!split) return SCGIB_EINVAL;
     release(reinterpret_cast<Split *>(split));

@@ -451,6 +451,7 @@ class _SCGIBCore(nn.Module):
             return u_gate.reshape(-1), u_feat
         if DEVICE_NOISE and self.hidden_dim == 64:
             return ops.device_noise(n, device)  # Philox on the device, one launch
+        ops.note_torch_rng()  # (a capture of this draw must be replayed by torch: ops.SplitGraph)
         return (torch.rand(n, device=device, dtype=torch.float32),
                 torch.rand(n, self.hidden_dim, device=device, dtype=torch.float32))
 

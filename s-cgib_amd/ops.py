@@ -286,6 +286,7 @@ def aside_guard(fn):
     @functools.wraps(fn)
     def wrapper(*args, **kwargs):
         check_handoff()  # an earlier step's hand-off wait gave up: raise, loud
+        _new_capture_clears_rng_mark()
         try:
             return fn(*args, **kwargs)
         except BaseException:
@@ -476,6 +477,43 @@ class SplitUnsupported(_lib.ScgibError):
 _SPLIT_SLOTS = 64  # hand-off slots per split (the pretraining step uses 2-3)
 _LIVE_SPLITS = weakref.WeakSet()
 
+# torch's generator inside a captured step: torch.cuda.CUDAGraph.replay()
+# advances the Philox offset the captured kernels read before every launch.
+# SplitGraph.replay() launches the lanes itself and never runs that update, so
+# a split replay of such a capture would draw the same numbers every step.
+# Whoever draws with torch's generator while a capture is under way calls
+# note_torch_rng(); the SplitGraph made next refuses (SplitUnsupported: the
+# callers replay the captured graph whole).  The mark holds the id of the
+# capture it was set in: a model forward (aside_guard) that finds itself in
+# another capture drops it, so an aborted capture does not reach a later split.
+_TORCH_RNG_CAPTURE = [None]
+
+
+def _capture_id():
+    """The id of the capture under way on the current stream, or None."""
+    if not torch.cuda.is_available() or not torch.cuda.is_current_stream_capturing():
+        return None
+    status, cid = ctypes.c_int(0), ctypes.c_ulonglong(0)
+    hip = ctypes.CDLL("libamdhip64.so")
+    if hip.hipStreamGetCaptureInfo(_stream(), ctypes.byref(status),
+                                   ctypes.byref(cid)) != 0:
+        return -1  # (capturing, id unknown: still a mark)
+    return int(cid.value)
+
+
+def note_torch_rng():
+    """Called where the model draws with torch's generator (models._noise)."""
+    cid = _capture_id()
+    if cid is not None:
+        _TORCH_RNG_CAPTURE[0] = cid
+
+
+def _new_capture_clears_rng_mark():
+    if _TORCH_RNG_CAPTURE[0] is not None:
+        cid = _capture_id()
+        if cid is not None and cid != _TORCH_RNG_CAPTURE[0]:
+            _TORCH_RNG_CAPTURE[0] = None
+
 
 class SplitGraph:
     """A captured step graph replayed as two linear lanes (csrc/graph_split.hip,
@@ -490,6 +528,12 @@ class SplitGraph:
 
     def __init__(self, graph, device):
         dev = torch.device(device)
+        rng, _TORCH_RNG_CAPTURE[0] = _TORCH_RNG_CAPTURE[0], None
+        if rng is not None:
+            raise SplitUnsupported(
+                "SplitGraph: the captured step drew with torch's RNG (torch.rand under capture: "
+                "models.DEVICE_NOISE off, or hidden_dim != 64); only CUDAGraph.replay() advances "
+                "that generator's offset, a split replay would repeat the same noise every step")
         self.graph = graph
         self.words = torch.zeros(4 * _SPLIT_SLOTS, dtype=torch.int32, device=dev)
         self._fault = handoff_fault_word(dev)
@@ -549,7 +593,11 @@ _Z_W1_OFF = _Z_SLAB
 # pair's backward leaves its final reduce jobs here instead of launching them,
 # and the step takes them; whatever no step took is reduced when the context
 # ends.  Only where nothing reads the gradients between the backward and the
-# step (the benches' replayed steps without a collective).
+# step (the benches' replayed steps without a collective).  The backward
+# defers only when every parameter of the pair has .grad None (autograd then
+# takes the weight-gradient views over without a kernel); the step checks
+# that the jobs' outputs are the gradients it steps on (optim.Adam._unaliased)
+# and takes the jobs only once its tensor table is built.
 FUSE_FINAL_ADAM = True
 # ... from this many slabs in the largest final job (the ego layer-0 weight-
 # gradient slabs).  0: always.  With four Adam elements per thread in the
@@ -1227,6 +1275,10 @@ class _GinEncoderPair(torch.autograd.Function):
         check_fork(main)
         ctx.lin = w0 is not None
         ctx.lin_leaves = (w0, b0)
+        # transfer_d's weight and both encoders' parameters: the ego chain's
+        # final reduce writes their gradients (backward: whether it may be
+        # left to the optimizer step)
+        ctx.final_leaves = tuple(p for p in (wt, *params) if isinstance(p, torch.Tensor))
         side.wait_stream(main)
         stamp("fwd.fork[main]")
         with torch.cuda.stream(side):
@@ -1360,9 +1412,19 @@ class _GinEncoderPair(torch.autograd.Function):
         final = getattr(ctx.sub[0], "final", None)
         if final is not None:  # the ego chain's weight-gradient reduce, d Wt(core) included
             ctx.sub[0].final = None
-            if _FINAL_ARMED[0]:  # left to the optimizer step that follows (fuse_final_into_step)
+            # left to the optimizer step that follows (fuse_final_into_step) — only
+            # when autograd will take the views of the buffers this reduce writes
+            # over as .grad (no kernel): with a .grad already there (gradient
+            # accumulation, zero_grad(set_to_none=False)) it adds them at once,
+            # before the deferred reduce has written them
+            if _FINAL_ARMED[0] and all(p.requires_grad and p.grad is None
+                                       for p in ctx.final_leaves):
                 _FINAL_PENDING.setdefault(main.device_index or 0, []).append(final)
             else:
+                # (an earlier backward's reduce still pending — accumulation
+                # that began from .grad None: autograd is about to read its output)
+                for jobs, _keep in _FINAL_PENDING.pop(main.device_index or 0, []):
+                    _reduce_jobs(jobs, _stream())
                 _reduce_jobs(final[0], _stream())
             final = None
         ctx.sub[0].dwt_row_slab = None

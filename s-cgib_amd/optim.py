@@ -55,6 +55,37 @@ class Adam(torch.optim.Optimizer):
                                        p.numel()))
         return out
 
+    def _unaliased(self, jobs, ents):
+        """The final reduces this step launches write the weight-gradient
+        buffers whose views the backward handed autograd; the step is right
+        only if those views ARE the gradients it steps on (autograd took them
+        over as .grad without a copy, and nobody re-bound .grad since).  Host
+        pointer arithmetic: every job's output range must lie inside the
+        (merged) gradient ranges of ``ents``.  Returns '' or a description of
+        the first range that does not, with the parameters it may belong to."""
+        spans = sorted((t.grad, t.grad + 4 * t.numel) for ent in ents for t in ent)
+        merged = []
+        for lo, hi in spans:
+            if merged and lo <= merged[-1][1]:
+                merged[-1][1] = max(merged[-1][1], hi)
+            else:
+                merged.append([lo, hi])
+        outs = [(j.out, j.out + 4 * j.width) for j in jobs]
+        for ji, (lo, hi) in enumerate(outs):
+            if any(a <= lo and hi <= b for a, b in merged):
+                continue
+            # the floats of this output no gradient covers, and the parameters
+            # of that size whose gradient lies outside every job's output
+            gap = (hi - lo - sum(max(0, min(hi, b) - max(lo, a)) for a, b in merged)) // 4
+            plist = [(gi, pi, p) for gi, group in enumerate(self.param_groups)
+                     for pi, p in enumerate(group["params"]) if p.grad is not None]
+            cand = [f"group {gi} parameter {pi} {tuple(p.shape)}" for gi, pi, p in plist
+                    if p.numel() == gap and not any(
+                        a <= p.grad.data_ptr() < b for a, b in outs)]
+            return (f"{gap} of the {(hi - lo) // 4} floats reduce job {ji} writes are no "
+                    f"parameter's .grad (un-aliased gradient: {', '.join(cand) or 'unknown'})")
+        return ""
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -62,18 +93,32 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        # every group's table first: an exception here (a sparse gradient, a CPU
+        # parameter) leaves the pending final reduces where the next step or the
+        # end of ops.fuse_final_into_step finds them
+        ents = [self._entries(group) for group in self.param_groups]
         pending = []  # the final weight-gradient reduces left to this step (ops.fuse_final_into_step)
         for group in self.param_groups:
             pending += ops.take_final(group["params"][0].device) if group["params"] else []
+        jobs = [j for jl, _ in pending for j in jl]
+        if jobs:
+            stale = self._unaliased(jobs, ents)
+            if stale:  # the reduces all the same (nothing is lost), no update
+                for jl, _ in pending:
+                    ops._reduce_jobs(jl, ops._stream())
+                raise _lib.ScgibError(
+                    "scgib Adam: a final weight-gradient reduce left to this step "
+                    "(ops.fuse_final_into_step) does not write the gradients it steps on: " + stale +
+                    ".  A .grad was copied or re-bound between the backward and the step; the "
+                    "reduces were launched, the parameters are unchanged")
         fused = False
         for gi, group in enumerate(self.param_groups):
-            ent = self._entries(group)
+            ent = ents[gi]
             if not ent:
                 continue
             dev = group["params"][0].device
             b1, b2 = group["betas"]
             st = ops._stream()
-            jobs = [j for jl, _ in pending for j in jl]
             if (jobs and not fused and len(self.param_groups) == 1 and len(ent) <= self._max
                     and len(jobs) <= int(_lib.query("scgib_adam_reduce_max_jobs"))
                     and max(j.n_slabs for j in jobs) >= ops.FUSE_FINAL_MIN_SLABS):
