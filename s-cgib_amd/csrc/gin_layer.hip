@@ -29,6 +29,8 @@
 //                    dW1 += dz1^T agg; d(agg) = dz1 W1.  Workgroups loop over
 //                    tiles and keep dW in MFMA accumulators; one slab each.
 //   slab_reduce_k  : fixed-order sum of the per-workgroup slabs.
+// gin_bwd_k (here) runs the d_in = 32 layers, the layer-0 fold and the head
+// MLP; d_in = 64 layers run gin_bwd5_k / 5z_k / 5r_k (gin_bwd5.h; BN: gin_bn.h).
 //
 // LDS tiles are row-major with a +1-float row pad (stride 65 / 33), which
 // makes every MFMA operand read (32 lanes: 32 rows of one column, or 32
@@ -37,423 +39,13 @@
 #include "contrast_body.h"
 #include "recon_fin.h"
 #include "running_update.h"
+#include "gin_bn.h"
 
 namespace scgib {
 
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
-// ---------------------------------------------------------------------------
-// BatchNorm finalize folded into the producing tile kernel (training mode).
-// Hierarchical last-arriver: the tiles of a layer arrive in groups of kGroup; the
-// last tile of a group combines the group's 16 tile statistics (fp64) into a
-// group partial, then arrives at the layer counter; the last group combines
-// the groups and writes the BN record / coefficients.  Two short load rounds
-// at the tail of the kernel replace a separate 1-workgroup finalize launch.
-// Fixed combination order -> deterministic.  Counters: caller-provided, zero
-// on entry; each is reset by its last arriver (graph-replay safe).
-// ---------------------------------------------------------------------------
-// tiles per BatchNorm statistics group (8 / 32 / 64 measured +1 %, round 1)
-constexpr int kGroup = 16;
-static_assert(kGroup % 4 == 0 && kGroup <= 64, "group combine: 4 partitions, <= 16 loads each");
-
-struct BnFwdFuse {          // gin_fwd_k: BN statistics + running update
-    unsigned *counters;     // [ngr_cap + 1]; nullptr: not fused (separate finalize)
-    double *gpart;          // [ngr_cap][128]: group sum, group centred M2
-    const float *gamma, *beta;
-    float *rmean, *rvar, *stat;
-    int64_t *nbt;
-    float eps, momentum;
-    int ngr_cap;
-    int defer;              // stop at the group partials (the consumer finishes)
-};
-
-struct BnBwdFuse {          // gin_bwd_stats_k: dgamma, dbeta, dz2 coefficients
-    unsigned *counters;
-    double *gpart;          // [ngr_cap][128]: group sum dy, group sum dy * xhat
-    float *dgamma, *dbeta, *coef;
-    int training, ngr_cap;
-    int defer;
-};
-
-// Cross-workgroup exchange: st_agent / ld_agent / block_arrive (common.h).
-
-// rows of tile t / group g of an n-row layer
-__device__ __forceinline__ double rows_in(int64_t n, int64_t first, int64_t span) {
-    const int64_t r = n - first;
-    return static_cast<double>(r < span ? r : span);
-}
-
-// Layer statistics from the ngr group partials (fp64, fixed order; 256
-// threads, channel c = tid & 63, partition p = tid >> 6 takes groups p, p + 4,
-// ...; one load round while ngr <= 64).  Every thread returns its channel's
-// mean and centred M2:  M2 = sum_g [M2_g + (S_g - n_g mean)^2 / n_g].
-// AGENT: the partials were written earlier in this kernel (agent-scope loads);
-// otherwise by a previous kernel (plain loads: L2-cached after the first
-// workgroup of an XCD, coherent across the kernel boundary).
-template <bool AGENT>
-__device__ __forceinline__ double ld_part(const double *p) {
-    if constexpr (AGENT) return ld_agent(p);
-    else return *p;
-}
-
-// Barrier-free layer combine (wave-local shuffles, no LDS): lane l of wave w
-// owns channel c = 16 w + (l & 15) and partition p = l >> 4, which takes
-// groups p, p + 4, ... (fp64, fixed order); the four partitions combine as
-// (p0 + p1) + (p2 + p3) through two xor shuffles (identical in every lane).
-// Split into the load (issue early, registers) and the combine, so other
-// loads can be in flight meanwhile; one load round for ngr <= kFinG.  (8:
-// the QM9 B512 ego layers' 28 groups in one round, and 32 fewer VGPRs than
-// 16 in the forward kernel, which then keeps its first neighbour-index round
-// in flight across the finish)
-constexpr int kFinR = 8, kFinG = 4 * kFinR;
-// backward consumers: 2 partitions x kBFinR groups per load round
-constexpr int kBFinR = 16;
-// past one round of 64 groups the last-arriver statistics take a third
-// level: 64-group supergroups (bn_fwd_hier / bn_bwd_hier)
-constexpr int kSuper = 64;
-
-struct FwdFin {
-    double vs[kFinR], vq[kFinR];
-};
-
-__device__ __forceinline__ int fin_channel() { return 16 * (threadIdx.x >> 6) + (threadIdx.x & 15); }
-
-template <bool AGENT>
-__device__ __forceinline__ void bn_fwd_fin_load(const double *__restrict__ gpart, int ngr, int g0,
-                                                FwdFin &f) {
-    const int c = fin_channel(), p = (threadIdx.x & 63) >> 4;
-#pragma unroll
-    for (int u = 0; u < kFinR; ++u) {
-        if (g0 + 4 * u < ngr) {  // wave-uniform: only rounds with a live group are loaded
-            const int64_t gg = g0 + p + 4 * u < ngr ? g0 + p + 4 * u : 0;  // group 0 always exists
-            f.vs[u] = ld_part<AGENT>(gpart + gg * 128 + c);
-            f.vq[u] = ld_part<AGENT>(gpart + gg * 128 + 64 + c);
-        }
-    }
-}
-
-__device__ __forceinline__ double quad_sum(double a) {
-    a = a + __shfl_xor(a, 16, kWave);
-    return a + __shfl_xor(a, 32, kWave);
-}
-
-// mean and centred M2 of channel fin_channel():
-//   mean = sum_g S_g / n,  M2 = sum_g [M2_g + (S_g - n_g mean)^2 / n_g]
-// n_g = kGroup * 64 for every group but possibly the last, and dividing by a power
-// of two equals multiplying by its reciprocal exactly, so only the last
-// group's term (added last by its owner, the same order) divides.
-// UNIT: rows of every entry but possibly the last (kGroup tiles; a 64-group
-// supergroup at the third level of bn_fwd_hier).  S (or nullptr): the sum.
-template <bool AGENT, int64_t UNIT = int64_t(kGroup) * TM>
-__device__ void bn_fwd_final(const double *__restrict__ gpart, int64_t n, int ngr, FwdFin &f,
-                             double &mean, double &M2, double *S = nullptr) {
-    constexpr double kFull = static_cast<double>(UNIT), kInvFull = 1.0 / kFull;
-    const int p = (threadIdx.x & 63) >> 4;
-    double a = 0.0;
-    for (int g0 = 0; g0 < ngr; g0 += kFinG) {
-        if (g0 > 0) bn_fwd_fin_load<AGENT>(gpart, ngr, g0, f);
-#pragma unroll
-        for (int u = 0; u < kFinR; ++u)
-            if (g0 + 4 * u < ngr) a += g0 + p + 4 * u < ngr ? f.vs[u] : 0.0;
-    }
-    const double sum = quad_sum(a);
-    if (S) *S = sum;
-    mean = sum / static_cast<double>(n);
-    const int glast = ngr - 1;
-    const double nlast = rows_in(n, int64_t(glast) * UNIT, UNIT);
-    const bool last_partial = nlast != kFull;
-    double q = 0.0, last_vq = 0.0, last_d = 0.0;
-    bool owns_last = false;
-    for (int g0 = 0; g0 < ngr; g0 += kFinG) {
-        if (ngr > kFinG) bn_fwd_fin_load<AGENT>(gpart, ngr, g0, f);  // else still in registers
-#pragma unroll
-        for (int u = 0; u < kFinR; ++u) {
-            if (g0 + 4 * u < ngr) {
-                const int g = g0 + p + 4 * u;
-                if (g < ngr) {
-                    if (g == glast && last_partial) {
-                        owns_last = true;
-                        last_vq = f.vq[u];
-                        last_d = f.vs[u] - nlast * mean;
-                    } else {
-                        const double d = f.vs[u] - kFull * mean;
-                        q += f.vq[u] + d * d * kInvFull;
-                    }
-                }
-            }
-        }
-    }
-    if (owns_last) q += last_vq + last_d * last_d / nlast;
-    M2 = quad_sum(q);
-}
-
-// BN record of channel c from (mean, M2): returns scale / shift; with
-// `write`, also the [4][64] record and the running-statistics update
-// (momentum, unbiased variance, num_batches_tracked += 1).
-// (gamma_c / beta_c are passed as values: load them early, a dependent
-// global load here costs a full memory latency)
-__device__ __forceinline__ float2 bn_fwd_publish(int c, double mean, double M2, int64_t n,
-                                                 float gamma_c, float beta_c,
-                                                 float eps, float momentum, float *rmean,
-                                                 float *rvar, int64_t *nbt, float *stat,
-                                                 bool write) {
-    const double var = M2 / static_cast<double>(n);
-    if (write && rmean) {
-        rmean[c] = static_cast<float>((1.0 - momentum) * rmean[c] + momentum * mean);
-        rvar[c] = static_cast<float>((1.0 - momentum) * rvar[c] +
-                                     momentum * (n > 1 ? M2 / static_cast<double>(n - 1) : M2));
-        if (c == 0 && nbt) *nbt += 1;
-    }
-    const double istd = 1.0 / sqrt(var + static_cast<double>(eps));
-    const double sc = gamma_c * istd;
-    const float scale = static_cast<float>(sc), shift = static_cast<float>(beta_c - mean * sc);
-    if (write) {
-        stat[c] = static_cast<float>(mean);
-        stat[64 + c] = static_cast<float>(istd);
-        stat[128 + c] = scale;
-        stat[192 + c] = shift;
-    }
-    return make_float2(scale, shift);
-}
-
-// A consumer of a deferred layer (scgib_bn_pending) that is not a GIN layer
-// (the encoder output's BN + ReLU): every 256-thread workgroup finishes the
-// statistics from the group partials; workgroup 0 writes the record and the
-// running update.  sSS[c] = scale, sSS[64 + c] = shift.  Call from all
-// threads, before any early return.
-__device__ __forceinline__ void bn_pending_finish(const scgib_bn_pending &pend, int64_t n,
-                                                  float *sSS) {
-    const int fc = fin_channel();
-    const int ngr = static_cast<int>(((n + TM - 1) / TM + kGroup - 1) / kGroup);
-    const float gam = pend.gamma[fc], bet = pend.beta[fc];
-    FwdFin fin;
-    bn_fwd_fin_load<false>(pend.gpart, ngr, 0, fin);
-    double mean, M2;
-    bn_fwd_final<false>(pend.gpart, n, ngr, fin, mean, M2);
-    const bool lead = (threadIdx.x & 63) < 16;
-    const float2 ss = bn_fwd_publish(fc, mean, M2, n, gam, bet, pend.eps, pend.momentum,
-                                     pend.running_mean, pend.running_var,
-                                     pend.num_batches_tracked, pend.stat, blockIdx.x == 0 && lead);
-    if (lead) {
-        sSS[fc] = ss.x;
-        sSS[64 + fc] = ss.y;
-    }
-    __syncthreads();
-}
-
-// 256 threads: channel c = tid & 63, partition p = tid >> 6 (4 partitions).
-// Per-tile (S, M2) -> group (S_g, M2_g) -> layer (mean, M2); exact
-// decomposition M2 = sum_b [M2_b + (S_b - n_b mean)^2 / n_b] at each level.
-// arrivals = tiles of group g whose statistics this workgroup contributes
-// (1 per tile kernel; a workgroup running several tiles of one group may
-// arrive for all of them at once)
-__device__ void bn_fwd_hier(const float *__restrict__ part, int64_t n, int64_t tile,
-                            const BnFwdFuse &fz, unsigned arrivals = 1u) {
-    const int64_t nt = (n + TM - 1) / TM;
-    const int ngr = static_cast<int>((nt + kGroup - 1) / kGroup);
-    const int g = static_cast<int>(tile / kGroup);
-    const int gsize = static_cast<int>(nt - int64_t(g) * kGroup < kGroup ? nt - int64_t(g) * kGroup : kGroup);
-    if (!block_arrive(&fz.counters[g], gsize, arrivals)) return;
-    const int c = threadIdx.x & 63, p = threadIdx.x >> 6;
-    __shared__ double sh[4][64];
-    __shared__ double smean[64];
-    {   // group combine: partition p takes tiles g*kGroup + p + 4u
-        constexpr int U = kGroup / 4;
-        float S[U], Q[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t t = int64_t(g) * kGroup + p + 4 * u;
-            const int64_t tc = p + 4 * u < gsize ? t : int64_t(g) * kGroup;
-            S[u] = ld_agent(part + tc * 128 + c);
-            Q[u] = ld_agent(part + tc * 128 + 64 + c);
-        }
-        double a = 0.0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) a += p + 4 * u < gsize ? static_cast<double>(S[u]) : 0.0;
-        sh[p][c] = a;
-        __syncthreads();
-        if (p == 0) {
-            const double sg = ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
-            smean[c] = sg / rows_in(n, int64_t(g) * kGroup * TM, kGroup * TM);
-            st_agent(fz.gpart + int64_t(g) * 128 + c, sg);
-        }
-        __syncthreads();
-        const double mg = smean[c];
-        double q = 0.0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (p + 4 * u < gsize) {
-                const int64_t t = int64_t(g) * kGroup + p + 4 * u;
-                const double nb = rows_in(n, t * TM, TM);
-                const double d = static_cast<double>(S[u]) - nb * mg;
-                q += static_cast<double>(Q[u]) + d * d / nb;
-            }
-        }
-        __syncthreads();
-        sh[p][c] = q;
-        __syncthreads();
-        if (p == 0) st_agent(fz.gpart + int64_t(g) * 128 + 64 + c, ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c]);
-        if (threadIdx.x == 0) fz.counters[g] = 0u;
-    }
-    if (fz.defer) return;  // the consumer kernel finishes (bn_fwd_final there)
-    double mean, M2;
-    FwdFin fin;
-    if (ngr > kSuper) {  // block-uniform
-        // more groups than one load round: a third level, so that no single
-        // workgroup walks every group partial in series at the end of the
-        // kernel (1172 groups at 1.2 M rows: ~74 us of dependent load rounds).
-        // The last group of each 64-group supergroup combines its groups
-        // (one round), the last supergroup combines the supergroups.
-        constexpr int64_t kSupRows = int64_t(kSuper) * kGroup * TM;
-        const int s = g / kSuper, nsup = (ngr + kSuper - 1) / kSuper;
-        const int ssize = ngr - s * kSuper < kSuper ? ngr - s * kSuper : kSuper;
-        unsigned *scnt = &fz.counters[fz.ngr_cap + 1 + s];
-        if (!block_arrive(scnt, ssize)) return;
-        const double *gp = fz.gpart + int64_t(s) * kSuper * 128;
-        double *sp = fz.gpart + int64_t(fz.ngr_cap) * 128;
-        const int64_t ns = static_cast<int64_t>(rows_in(n, s * kSupRows, kSupRows));
-        double S;
-        bn_fwd_fin_load<true>(gp, ssize, 0, fin);
-        bn_fwd_final<true>(gp, ns, ssize, fin, mean, M2, &S);
-        if ((threadIdx.x & 63) < 16) {
-            st_agent(sp + int64_t(s) * 128 + fin_channel(), S);
-            st_agent(sp + int64_t(s) * 128 + 64 + fin_channel(), M2);
-        }
-        if (threadIdx.x == 0) *scnt = 0u;
-        if (!block_arrive(&fz.counters[fz.ngr_cap], nsup)) return;
-        const float gam = fz.gamma[fin_channel()], bet = fz.beta[fin_channel()];
-        bn_fwd_fin_load<true>(sp, nsup, 0, fin);
-        bn_fwd_final<true, kSupRows>(sp, n, nsup, fin, mean, M2);
-        bn_fwd_publish(fin_channel(), mean, M2, n, gam, bet, fz.eps, fz.momentum, fz.rmean,
-                       fz.rvar, fz.nbt, fz.stat, (threadIdx.x & 63) < 16);
-        if (threadIdx.x == 0) fz.counters[fz.ngr_cap] = 0u;
-        return;
-    }
-    if (!block_arrive(&fz.counters[fz.ngr_cap], ngr)) return;
-    const float gam = fz.gamma[fin_channel()], bet = fz.beta[fin_channel()];
-    bn_fwd_fin_load<true>(fz.gpart, ngr, 0, fin);
-    bn_fwd_final<true>(fz.gpart, n, ngr, fin, mean, M2);
-    bn_fwd_publish(fin_channel(), mean, M2, n, gam, bet, fz.eps, fz.momentum, fz.rmean,
-                   fz.rvar, fz.nbt, fz.stat, (threadIdx.x & 63) < 16);
-    if (threadIdx.x == 0) fz.counters[fz.ngr_cap] = 0u;
-}
-
-// Layer sums (dbeta | dgamma, 128 values) from the ngr group partials,
-// barrier-free: lane l of wave w owns sum index cs = 32 w + (l & 31) and
-// partition p = l >> 5 (groups p, p + 2, ...); p0 + p1 via one xor shuffle.
-struct BwdFin {
-    double v[kBFinR];
-};
-
-__device__ __forceinline__ int bfin_index() { return 32 * (threadIdx.x >> 6) + (threadIdx.x & 31); }
-
-template <bool AGENT>
-__device__ __forceinline__ void bn_bwd_fin_load(const double *__restrict__ gpart, int ngr, int g0,
-                                                BwdFin &f) {
-    const int cs = bfin_index(), p = (threadIdx.x & 63) >> 5;
-#pragma unroll
-    for (int u = 0; u < kBFinR; ++u) {
-        if (g0 + 2 * u < ngr) {  // wave-uniform
-            const int64_t gg = g0 + p + 2 * u < ngr ? g0 + p + 2 * u : 0;  // group 0 always exists
-            f.v[u] = ld_part<AGENT>(gpart + gg * 128 + cs);
-        }
-    }
-}
-
-template <bool AGENT>
-__device__ double bn_bwd_final(const double *__restrict__ gpart, int ngr, BwdFin &f) {
-    const int p = (threadIdx.x & 63) >> 5;
-    double a = 0.0;
-    for (int g0 = 0; g0 < ngr; g0 += 2 * kBFinR) {
-        if (g0 > 0) bn_bwd_fin_load<AGENT>(gpart, ngr, g0, f);
-#pragma unroll
-        for (int u = 0; u < kBFinR; ++u)
-            if (g0 + 2 * u < ngr) a += g0 + p + 2 * u < ngr ? f.v[u] : 0.0;
-    }
-    return a + __shfl_xor(a, 32, kWave);
-}
-
-// dbeta = sum dy (c < 64), dgamma = sum dy xhat (c >= 64); dz2 coefficient
-// coef[c] = tot / N in training (0 in eval); coef may be nullptr
-__device__ __forceinline__ float bn_bwd_publish(int c, double tot, int64_t n, int training,
-                                                float *dgamma, float *dbeta, float *coef) {
-    const float cf = training ? static_cast<float>(tot / static_cast<double>(n)) : 0.f;
-    if (dbeta) {
-        if (c < 64) dbeta[c] = static_cast<float>(tot);
-        else dgamma[c - 64] = static_cast<float>(tot);
-    }
-    if (coef) coef[c] = cf;
-    return cf;
-}
-
-// backward: tile (sum dy, sum dy xhat) -> group -> layer sums (fp64);
-// sh: 2 KB of LDS scratch (the caller's, so a kernel near its LDS limit can
-// lend a dead tile image)
-// (group g, `count` of its tiles arriving at once: gin_bwd_statsz_k's walk)
-__device__ __forceinline__ void bn_bwd_hier_gs(const float *__restrict__ part, int64_t n, int g, unsigned count,
-                               const BnBwdFuse &bz, double (*sh)[128]) {
-    const int64_t nt = (n + TM - 1) / TM;
-    const int ngr = static_cast<int>((nt + kGroup - 1) / kGroup);
-    const int gsize = static_cast<int>(nt - int64_t(g) * kGroup < kGroup ? nt - int64_t(g) * kGroup : kGroup);
-    if (!block_arrive(&bz.counters[g], gsize, count)) return;
-    const int c = threadIdx.x & 127, p = threadIdx.x >> 7;  // 128 sums x 2 partitions
-    {
-        constexpr int U = kGroup / 2;
-        float v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = p + 2 * u;
-            v[u] = ld_agent(part + (int64_t(g) * kGroup + (k < gsize ? k : 0)) * 128 + c);
-        }
-        double a = 0.0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) a += p + 2 * u < gsize ? static_cast<double>(v[u]) : 0.0;
-        sh[p][c] = a;
-        __syncthreads();
-        if (p == 0) st_agent(bz.gpart + int64_t(g) * 128 + c, sh[0][c] + sh[1][c]);
-        if (threadIdx.x == 0) bz.counters[g] = 0u;
-    }
-    if (bz.defer) return;  // the layer's gin_bwd_k finishes (bn_bwd_final there)
-    BwdFin fin;
-    if (ngr > kSuper) {  // block-uniform: the third level, as in bn_fwd_hier
-        const int s = g / kSuper, nsup = (ngr + kSuper - 1) / kSuper;
-        const int ssize = ngr - s * kSuper < kSuper ? ngr - s * kSuper : kSuper;
-        unsigned *scnt = &bz.counters[bz.ngr_cap + 1 + s];
-        if (!block_arrive(scnt, ssize)) return;
-        const double *gp = bz.gpart + int64_t(s) * kSuper * 128;
-        double *sp = bz.gpart + int64_t(bz.ngr_cap) * 128;
-        bn_bwd_fin_load<true>(gp, ssize, 0, fin);
-        const double st = bn_bwd_final<true>(gp, ssize, fin);
-        if ((threadIdx.x & 63) < 32) st_agent(sp + int64_t(s) * 128 + bfin_index(), st);
-        if (threadIdx.x == 0) *scnt = 0u;
-        if (!block_arrive(&bz.counters[bz.ngr_cap], nsup)) return;
-        bn_bwd_fin_load<true>(sp, nsup, 0, fin);
-        const double tot = bn_bwd_final<true>(sp, nsup, fin);
-        if ((threadIdx.x & 63) < 32)
-            bn_bwd_publish(bfin_index(), tot, n, bz.training, bz.dgamma, bz.dbeta, bz.coef);
-        if (threadIdx.x == 0) bz.counters[bz.ngr_cap] = 0u;
-        return;
-    }
-    if (!block_arrive(&bz.counters[bz.ngr_cap], ngr)) return;
-    bn_bwd_fin_load<true>(bz.gpart, ngr, 0, fin);
-    const double tot = bn_bwd_final<true>(bz.gpart, ngr, fin);
-    if ((threadIdx.x & 63) < 32)
-        bn_bwd_publish(bfin_index(), tot, n, bz.training, bz.dgamma, bz.dbeta, bz.coef);
-    if (threadIdx.x == 0) bz.counters[bz.ngr_cap] = 0u;
-}
-
-__device__ void bn_bwd_hier_s(const float *__restrict__ part, int64_t n, int64_t tile,
-                              const BnBwdFuse &bz, double (*sh)[128]) {
-    bn_bwd_hier_gs(part, n, static_cast<int>(tile / kGroup), 1u, bz, sh);
-}
-
-__device__ void bn_bwd_hier(const float *__restrict__ part, int64_t n, int64_t tile,
-                            const BnBwdFuse &bz) {
-    __shared__ double sh[2][128];
-    bn_bwd_hier_s(part, n, tile, bz, sh);
-}
-
 // ---------------------------------------------------------------------------
 // transfer_d folded into the first GIN layer (PRE): the reference computes
 // h0 = x Wt^T per node (models.py:668-669, :1164-1165) and then aggregates h0;
@@ -1356,12 +948,7 @@ __global__ __launch_bounds__(256, (DIN <= 64 && !RECON ? 2 : 1)) void gin_bwd_k(
             c2 = ld4(coef + 64 + 4 * c4);
         } else {  // finish the sums; workgroup 0 writes dgamma, dbeta
             __shared__ float sCoef[128];
-            const double tot = bn_bwd_final<false>(pend.gpart, pend_ngr, bfin);
-            const int cs = bfin_index();
-            const bool lead = (tid & 63) < 32, w0 = blockIdx.x == 0 && lead;
-            const float cf = bn_bwd_publish(cs, tot, n, pend.training, w0 ? pend.dgamma : nullptr,
-                                            w0 ? pend.dbeta : nullptr, nullptr);
-            if (lead) sCoef[cs] = cf;
+            bn_bwd_pending_finish(pend, pend_ngr, n, bfin, sCoef);
             __syncthreads();
             c1 = make_float4(sCoef[4 * c4], sCoef[4 * c4 + 1], sCoef[4 * c4 + 2], sCoef[4 * c4 + 3]);
             c2 = make_float4(sCoef[64 + 4 * c4], sCoef[65 + 4 * c4], sCoef[66 + 4 * c4],
@@ -1577,425 +1164,9 @@ __global__ __launch_bounds__(256, (DIN <= 64 && !RECON ? 2 : 1)) void gin_bwd_k(
     SCGIB_MARK(4);
 }
 
-
-// ---------------------------------------------------------------------------
-// gin_bwd5_k: the GIN layer backward (BN, d_in = 64) on 32-row sub-tiles,
-// TWO workgroups per CU (63 KB LDS, <= 256 VGPRs).
-//
-// (Round 2 replaced gin_bwd2_k with it: 64-row tiles at one workgroup per
-// CU, ~1.7 tiles per CU at QM9 B512, whose per-tile phases left the matrix
-// pipe idle ~40 % of a tile and whose dword operand reads ran the GEMMs at
-// ~80 % of the MFMA rate; phase trace r02.)  Here:
-//   * 32-row sub-tiles, two workgroups per CU: one workgroup's non-MFMA
-//     phases run under the other's MFMAs; ~3.4 sub-tiles per CU balance
-//     better than 1.7 tiles;
-//   * no K split: waves take whole products, 32 MFMAs per wave and pair:
-//       pair A: waves 0,1 (N): dr block q = dz2 W2[:, 32q..] (K = 64, one
-//               chain), dz1 = dr [r > 0] written straight from the accumulator;
-//               waves 2,3 (T): dW2 rows 32q.. += dz2^T r (two blocks, K = 32 rows)
-//       pair B: N: dW1 rows 32q.. += dz1^T agg;  T: d(agg) block q = dz1 W1[:, 32q..]
-//   * every MFMA operand is fed four k values per ds_read_b128 (mma_rk4 /
-//     mma_kk4x2, permuted k order): NN products read dz row-major and take
-//     the wave's 32-column weight block from 32 VGPRs held for the whole
-//     kernel (no weight image in LDS); TN products read transposed dz, r and
-//     agg images [col][row];
-//   * the next sub-tile's rows are loaded into registers before pair A and
-//     written to the r^T / agg^T images once their last reader has passed a
-//     barrier (r after pair A, agg after pair B): three barriers per sub-tile.
-// The elementwise steps own one column and eight rows per thread (c = tid &
-// 63, rows 8 w..8 w+7), so the transposed images are written as float4 runs
-// and the row-major dz images as conflict-free dwords.
-// LDS: dz2, dz1 row-major + transposed, r^T, agg^T, d(agg) staging = 63 KB.
-// ---------------------------------------------------------------------------
-constexpr int SM = 32;   // rows per sub-tile
-constexpr int LDR = 68;  // row-major 64-wide images (= 4 mod 64: b128 reads conflict free)
-constexpr int LDT = 36;  // transposed [64][32] images (rows k-contiguous)
-
-// WG = false: a frozen layer (the fine-tune freezing quirk, models.py:424-434:
-// no parameter of it takes a gradient) — only the data-gradient chains run,
-// dr and d(agg), each exactly as with WG (bitwise the same d(agg)); the
-// dW products, the agg rows (read only by dW1), the transposed dz images
-// and the slab are skipped.
-template <int DIN, bool WG = true>
-__global__ __launch_bounds__(256, 2) void gin_bwd5_k(
-    const float *__restrict__ dy, const float *__restrict__ z2, const float *__restrict__ r,
-    const float *__restrict__ agg, const float *__restrict__ stat,
-    const float *__restrict__ coef, const float *__restrict__ w1, const float *__restrict__ w2,
-    int64_t ncap, int64_t nsub, float *__restrict__ dagg_out, float *__restrict__ slab,
-    const int32_t *__restrict__ dims, scgib_bn_bwd_pending pend) {
-    static_assert(DIN == 64 && SM == 32, "64-wide rows, 32-row sub-tiles");
-    constexpr int SLAB = 64 * 64 + 64 * DIN + 128;
-    __shared__ __attribute__((aligned(16))) float sD[SM * LDR];   // dz2 [row][k]
-    __shared__ __attribute__((aligned(16))) float sDT[64 * LDT];  // dz2 [col][row]
-    __shared__ __attribute__((aligned(16))) float sE[SM * LDR];   // dz1
-    __shared__ __attribute__((aligned(16))) float sET[64 * LDT];
-    __shared__ __attribute__((aligned(16))) float sRT[64 * LDT];  // r [col][row]
-    __shared__ __attribute__((aligned(16))) float sAT[DIN * LDT]; // agg [col][row]
-    __shared__ float sG[SM * LDH];                                 // d(agg) staging
-    __shared__ float sCoef[128];
-    const int64_t n = eff_count(dims, 0, ncap);
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
-    const int kk = l >> 5, li = l & 31;
-    const bool nw = w < 2;  // wave-uniform role: N (dr, dW1) or T (dW2, d(agg))
-    const int q = w & 1;    // the role's 32-wide block
-    const int c = l;        // elementwise: column c, rows 8 w .. 8 w + 7
-    const int64_t last = ncap - 1;
-    const int64_t G = gridDim.x;
-    SCGIB_MARK(0);
-    SCGIB_MARK_HWID();
-    BwdFin bfin;
-    const int pend_ngr = static_cast<int>(((n + TM - 1) / TM + kGroup - 1) / kGroup);
-    if (pend.gpart) bn_bwd_fin_load<false>(pend.gpart, pend_ngr, 0, bfin);
-    const float s_mean = stat[c], s_istd = stat[64 + c], s_sc = stat[128 + c];
-    float c1 = 0.f, c2 = 0.f;
-    if (!pend.gpart) {
-        c1 = coef[c];
-        c2 = coef[64 + c];
-    }
-    // the wave's weight block: N waves W2[:, 32q..] (dr), T waves W1[:, 32q..] (d(agg))
-    float wreg[32];
-    {
-        const float *wm = nw ? w2 : w1;
-#pragma unroll
-        for (int s = 0; s < 32; ++s) wreg[s] = wm[kperm(s, kk) * 64 + q * 32 + li];
-    }
-    float nx[4][8];  // a sub-tile's column c, rows 8 w + i: [0] dy, [1] z2, [2] r, [3] agg
-    auto load_sub = [&](int64_t s) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {  // in order of use: r, agg, then dy / z2
-            int64_t row = s * SM + 8 * w + i;
-            row = row < last ? row : last;
-            nx[2][i] = r[row * 64 + c];
-        }
-        if constexpr (WG) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                int64_t row = s * SM + 8 * w + i;
-                row = row < last ? row : last;
-                nx[3][i] = agg[row * DIN + c];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            int64_t row = s * SM + 8 * w + i;
-            row = row < last ? row : last;
-            nx[0][i] = dy[row * 64 + c];
-            nx[1][i] = z2[row * 64 + c];
-        }
-    };
-    auto put_t = [&](float *img, int a) {  // column c, rows 8w..8w+7 -> [c][row]
-        float4 *p = reinterpret_cast<float4 *>(img + c * LDT + 8 * w);
-        p[0] = make_float4(nx[a][0], nx[a][1], nx[a][2], nx[a][3]);
-        p[1] = make_float4(nx[a][4], nx[a][5], nx[a][6], nx[a][7]);
-    };
-    auto rows_of = [&](int64_t s) {
-        const int64_t v = n - s * SM;
-        return static_cast<int>(v < SM ? (v > 0 ? v : 0) : SM);
-    };
-    auto zero_pad = [&](int64_t s, int from) {
-        const int64_t row0 = s * SM;
-        const int ncr = static_cast<int>(ncap - row0 < SM ? ncap - row0 : SM);
-        for (int idx = from * DIN + tid; idx < ncr * DIN; idx += 256) dagg_out[row0 * DIN + idx] = 0.f;
-    };
-    int64_t s = blockIdx.x;
-    int nv = s < nsub ? rows_of(s) : 0;
-    if (nv > 0) load_sub(s);
-    if (pend.gpart) {  // finish the BN-backward sums; workgroup 0 writes dgamma, dbeta
-        const double tot = bn_bwd_final<false>(pend.gpart, pend_ngr, bfin);
-        const int cs = bfin_index();
-        const bool lead = (tid & 63) < 32, w0 = blockIdx.x == 0 && lead;
-        const float cf = bn_bwd_publish(cs, tot, n, pend.training, w0 ? pend.dgamma : nullptr,
-                                        w0 ? pend.dbeta : nullptr, nullptr);
-        if (lead) sCoef[cs] = cf;
-    }
-    if (nv > 0) {
-        put_t(sRT, 2);
-        if (WG) put_t(sAT, 3);
-    }
-    // the weight registers complete here: a load still counted at the loop
-    // entry makes hipcc wait vmcnt(0..3) at their uses in EVERY iteration
-    // (then for the next sub-tile's rows)
-    vm_wait_all();
-    __syncthreads();
-    if (pend.gpart) {
-        c1 = sCoef[c];
-        c2 = sCoef[64 + c];
-    }
-    const float k1 = s_istd * c2;  // dz2 = sc (dy - c1 - (z2 - mean) istd c2)
-    SCGIB_MARK(1);
-    // N waves: dW1 blocks (q, 0), (q, 1) and db1; T waves: dW2 blocks and db2
-    f32x16 accA = zero16(), accB = zero16();
-    float dbias = 0.f;
-    for (int it = 0; s < nsub; s += G, ++it) {
-        if (nv == 0) {  // capacity tail: this and every later sub-tile is padding
-            for (int64_t t = s; t < nsub; t += G) zero_pad(t, rows_of(t));
-            break;
-        }
-        {   // dz2 (rows past nv zero) -> sD row-major and sDT transposed
-            float d[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float v = s_sc * (nx[0][i] - c1 - (nx[1][i] - s_mean) * k1);
-                d[i] = 8 * w + i < nv ? v : 0.f;
-                sD[(8 * w + i) * LDR + c] = d[i];
-            }
-            if constexpr (WG) {
-                float4 *p = reinterpret_cast<float4 *>(sDT + c * LDT + 8 * w);
-                p[0] = make_float4(d[0], d[1], d[2], d[3]);
-                p[1] = make_float4(d[4], d[5], d[6], d[7]);
-            }
-        }
-        const int64_t next = s + G;
-        const int next_nv = next < nsub ? rows_of(next) : 0;  // block-uniform
-        if (next_nv > 0) load_sub(next);  // in flight during both product pairs
-        lds_barrier();  // dz2 complete
-        if (it == 0) SCGIB_MARK(2);
-        if (nw) {  // dr block q, dz1 = dr [r > 0] -> sE, sET (mask by multiplication)
-            const f32x16 dr = mma_rk4<8>(sD + li * LDR + 4 * kk, wreg, zero16());
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int row = acc_row(reg, l), col = q * 32 + li;
-                const float v = dr[reg] * (sRT[col * LDT + row] > 0.f ? 1.f : 0.f);
-                sE[row * LDR + col] = v;
-                if (WG) sET[col * LDT + row] = v;
-            }
-        } else if constexpr (WG) {   // dW2 rows 32q.. += dz2^T r (db2 from the A operand)
-            mma_kk4x2<4>(sDT + (q * 32 + li) * LDT + 4 * kk, sRT + li * LDT + 4 * kk,
-                         sRT + (32 + li) * LDT + 4 * kk, accA, accB, dbias);
-        }
-        lds_barrier();  // dz1 complete; r and dz2 consumed
-        if (it == 0) SCGIB_MARK(3);
-        if (next_nv > 0) put_t(sRT, 2);
-        if (nw) {  // dW1 rows 32q.. += dz1^T agg (db1 from the A operand)
-            if constexpr (WG)
-                mma_kk4x2<4>(sET + (q * 32 + li) * LDT + 4 * kk, sAT + li * LDT + 4 * kk,
-                             sAT + (32 + li) * LDT + 4 * kk, accA, accB, dbias);
-        } else {   // d(agg) block q = dz1 W1[:, 32q..] -> staging
-            const f32x16 da = mma_rk4<8>(sE + li * LDR + 4 * kk, wreg, zero16());
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) sG[acc_row(reg, l) * LDH + q * 32 + li] = da[reg];
-        }
-        lds_barrier();  // d(agg) staged; agg and dz1 consumed
-        if (it == 0) SCGIB_MARK(4);
-        if (WG && next_nv > 0) put_t(sAT, 3);
-        // d(agg) rows: full-row float4 stores (after the loads: in-order vmcnt)
-        {
-            const int c4 = tid & 15, rs = tid >> 4;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int rr = rs + 16 * k;
-                const float *pg = sG + rr * LDH + 4 * c4;
-                const float4 v = make_float4(pg[0], pg[1], pg[2], pg[3]);
-                if (rr < nv) st4(dagg_out + (s * SM + rr) * DIN + 4 * c4, v);
-            }
-        }
-        if (dims) zero_pad(s, nv);
-        nv = next_nv;
-    }
-    SCGIB_MARK(5);
-    if constexpr (!WG) return;
-    // per-workgroup slab: dW2 | dW1 | db2 | db1 (gin_bwd_k layout)
-    float *sl = slab + static_cast<int64_t>(blockIdx.x) * SLAB;
-    float *dw = nw ? sl + 64 * 64 : sl;  // N: dW1 [64][DIN], T: dW2 [64][64]
-    const int ld = nw ? DIN : 64;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int j = q * 32 + acc_row(reg, l);
-        dw[j * ld + li] = accA[reg];
-        dw[j * ld + 32 + li] = accB[reg];
-    }
-    dbias += __shfl_xor(dbias, 32, kWave);
-    if (l < 32) sl[64 * 64 + 64 * DIN + (nw ? 64 : 0) + q * 32 + l] = dbias;
-    SCGIB_MARK(6);
-}
-
-// ---------------------------------------------------------------------------
-// The agg-free backward of a d_in = 64 GIN layer l >= 1.
-// agg_l = (I + A) h_{l-1} is read by exactly one product of the layer's
-// backward, dW1 = dz1^T agg.  A is symmetric (the reference's bidirected
-// molecule graphs), so with g = (I + A)^T dz1 — the transposed gather the
-// NEXT statistics kernel runs anyway, now over dz1 instead of d(agg):
-//   dW1_l      = dz1^T (I + A) h_{l-1} = g^T h_{l-1}
-//   d h_{l-1}  = (I + A)^T (dz1 W1) = g W1
-// and h_{l-1} = relu(scale z2_{l-1} + shift) comes elementwise from the z2
-// rows that kernel reads for layer l-1's BatchNorm backward.  So the forward
-// stores no agg for these layers (256 B per row less of the 768 B it wrote,
-// gin_fwd_k), gin_bwd5z_k runs two of gin_bwd5_k's four products (dr, dW2)
-// and writes dz1 where gin_bwd5_k wrote d(agg), reading no agg; and
-// gin_bwd_statsz_k gathers dz1 and adds the two products it moved (g W1 and
-// g^T h, f32 MFMA), leaving dW1 as per-workgroup partials.  No flops are
-// added, only moved; the sums associate differently, so results match the
-// stored-agg path to rounding, not bitwise (ops.AGG_FREE selects the path).
-// ---------------------------------------------------------------------------
-constexpr int kZSlab = 64 * 64 + 128;  // gin_bwd5z_k slab: dW2 [64][64] | db2 | db1
-
-// gin_bwd5z_k: gin_bwd5_k's sub-tile walk with its first product pair only —
-//   waves 0,1 (N): dr block q = dz2 W2[:, 32q..] (K = 64), dz1 = dr [r > 0]
-//                  -> dz1 staging (row-major) and db1 (column sums of dz1);
-//   waves 2,3 (T): dW2 rows 32q.. += dz2^T r (two blocks, K = 32 rows) + db2
-// — then the dz1 rows go out as full-row float4 stores: two barriers per
-// sub-tile (gin_bwd5_k: three), no agg rows loaded, no W1.
-// WG = false: a frozen layer (the fine-tune freezing quirk) — dz1 by the same
-// dr chain, no dW2 / db products, no slab.
-template <bool WG = true>
-__global__ __launch_bounds__(256, 2) void gin_bwd5z_k(
-    const float *__restrict__ dy, const float *__restrict__ z2, const float *__restrict__ r,
-    const float *__restrict__ stat, const float *__restrict__ coef, const float *__restrict__ w2,
-    int64_t ncap, int64_t nsub, int64_t G, float *__restrict__ dz1_out, float *__restrict__ slab,
-    const int32_t *__restrict__ dims, scgib_bn_bwd_pending pend, scgib_slab_job fold,
-    scgib_slab_job fold2) {
-    static_assert(SM == 32, "32-row sub-tiles");
-    __shared__ __attribute__((aligned(16))) float sD[SM * LDR];   // dz2 [row][k]
-    __shared__ __attribute__((aligned(16))) float sDT[64 * LDT];  // dz2 [col][row]
-    __shared__ __attribute__((aligned(16))) float sRT[64 * LDT];  // r [col][row]
-    __shared__ float sE[SM * LDH];                                 // dz1 staging
-    __shared__ float sCoef[128];
-    if (static_cast<int64_t>(blockIdx.x) >= G) {  // block-uniform: a folded reduce block
-        const int b = static_cast<int>(blockIdx.x - G), f1 = slab_fold8_blocks(fold);
-        if (b < f1) slab_fold8_block(fold, b, sD);
-        else slab_fold_block(fold2, b - f1, sD);
-        return;
-    }
-    const int64_t n = eff_count(dims, 0, ncap);
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
-    const int kk = l >> 5, li = l & 31;
-    const bool nw = w < 2;  // wave-uniform role: N (dr, dz1, db1) or T (dW2, db2)
-    const int q = w & 1;    // the role's 32-wide block
-    const int c = l;        // elementwise: column c, rows 8 w .. 8 w + 7
-    const int64_t last = ncap - 1;
-    SCGIB_MARK(0);
-    SCGIB_MARK_HWID();
-    BwdFin bfin;
-    const int pend_ngr = static_cast<int>(((n + TM - 1) / TM + kGroup - 1) / kGroup);
-    if (pend.gpart) bn_bwd_fin_load<false>(pend.gpart, pend_ngr, 0, bfin);
-    const float s_mean = stat[c], s_istd = stat[64 + c], s_sc = stat[128 + c];
-    float c1 = 0.f, c2 = 0.f;
-    if (!pend.gpart) {
-        c1 = coef[c];
-        c2 = coef[64 + c];
-    }
-    float wreg[32];  // N waves: W2[:, 32q..] (k in kperm order); T waves: unused
-#pragma unroll
-    for (int s = 0; s < 32; ++s) wreg[s] = nw ? w2[kperm(s, kk) * 64 + q * 32 + li] : 0.f;
-    float nx[3][8];  // a sub-tile's column c, rows 8 w + i: [0] dy, [1] z2, [2] r
-    auto load_sub = [&](int64_t s) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {  // in order of use: r, then dy / z2
-            int64_t row = s * SM + 8 * w + i;
-            row = row < last ? row : last;
-            nx[2][i] = r[row * 64 + c];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            int64_t row = s * SM + 8 * w + i;
-            row = row < last ? row : last;
-            nx[0][i] = dy[row * 64 + c];
-            nx[1][i] = z2[row * 64 + c];
-        }
-    };
-    auto put_rt = [&]() {  // r: column c, rows 8w..8w+7 -> [c][row]
-        float4 *p = reinterpret_cast<float4 *>(sRT + c * LDT + 8 * w);
-        p[0] = make_float4(nx[2][0], nx[2][1], nx[2][2], nx[2][3]);
-        p[1] = make_float4(nx[2][4], nx[2][5], nx[2][6], nx[2][7]);
-    };
-    auto rows_of = [&](int64_t s) {
-        const int64_t v = n - s * SM;
-        return static_cast<int>(v < SM ? (v > 0 ? v : 0) : SM);
-    };
-    auto zero_pad = [&](int64_t s, int from) {
-        const int64_t row0 = s * SM;
-        const int ncr = static_cast<int>(ncap - row0 < SM ? ncap - row0 : SM);
-        for (int idx = from * 64 + tid; idx < ncr * 64; idx += 256) dz1_out[row0 * 64 + idx] = 0.f;
-    };
-    int64_t s = blockIdx.x;
-    int nv = s < nsub ? rows_of(s) : 0;
-    if (nv > 0) load_sub(s);
-    if (pend.gpart) {  // finish the BN-backward sums; workgroup 0 writes dgamma, dbeta
-        const double tot = bn_bwd_final<false>(pend.gpart, pend_ngr, bfin);
-        const int cs = bfin_index();
-        const bool lead = (tid & 63) < 32, w0 = blockIdx.x == 0 && lead;
-        const float cf = bn_bwd_publish(cs, tot, n, pend.training, w0 ? pend.dgamma : nullptr,
-                                        w0 ? pend.dbeta : nullptr, nullptr);
-        if (lead) sCoef[cs] = cf;
-    }
-    if (nv > 0) put_rt();
-    vm_wait_all();  // the weight registers complete before the loop (gin_bwd5_k)
-    __syncthreads();
-    if (pend.gpart) {
-        c1 = sCoef[c];
-        c2 = sCoef[64 + c];
-    }
-    const float k1 = s_istd * c2;  // dz2 = sc (dy - c1 - (z2 - mean) istd c2)
-    SCGIB_MARK(1);
-    f32x16 accA = zero16(), accB = zero16();  // T waves: dW2 blocks (q, 0), (q, 1)
-    float dbias = 0.f;                         // N: db1 (column q*32 + li), T: db2
-    for (int it = 0; s < nsub; s += G, ++it) {
-        if (nv == 0) {  // capacity tail: this and every later sub-tile is padding
-            for (int64_t t = s; t < nsub; t += G) zero_pad(t, rows_of(t));
-            break;
-        }
-        {   // dz2 (rows past nv zero) -> sD row-major and sDT transposed
-            float d[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float v = s_sc * (nx[0][i] - c1 - (nx[1][i] - s_mean) * k1);
-                d[i] = 8 * w + i < nv ? v : 0.f;
-                sD[(8 * w + i) * LDR + c] = d[i];
-            }
-            float4 *p = reinterpret_cast<float4 *>(sDT + c * LDT + 8 * w);
-            p[0] = make_float4(d[0], d[1], d[2], d[3]);
-            p[1] = make_float4(d[4], d[5], d[6], d[7]);
-        }
-        const int64_t next = s + G;
-        const int next_nv = next < nsub ? rows_of(next) : 0;  // block-uniform
-        if (next_nv > 0) load_sub(next);  // in flight during the products
-        lds_barrier();  // dz2 complete
-        if (it == 0) SCGIB_MARK(2);
-        if (nw) {  // dr block q, dz1 = dr [r > 0] (mask by multiplication) -> staging
-            const f32x16 dr = mma_rk4<8>(sD + li * LDR + 4 * kk, wreg, zero16());
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int row = acc_row(reg, l), col = q * 32 + li;
-                const float v = dr[reg] * (sRT[col * LDT + row] > 0.f ? 1.f : 0.f);
-                sE[row * LDH + col] = v;
-                dbias += v;
-            }
-        } else if constexpr (WG) {   // dW2 rows 32q.. += dz2^T r (db2 from the A operand)
-            mma_kk4x2<4>(sDT + (q * 32 + li) * LDT + 4 * kk, sRT + li * LDT + 4 * kk,
-                         sRT + (32 + li) * LDT + 4 * kk, accA, accB, dbias);
-        }
-        lds_barrier();  // dz1 staged; r and dz2 consumed
-        if (it == 0) SCGIB_MARK(3);
-        if (next_nv > 0) put_rt();
-        {   // dz1 rows: full-row float4 stores
-            const int c4 = tid & 15, rs = tid >> 4;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int rr = rs + 16 * k;
-                const float *pg = sE + rr * LDH + 4 * c4;
-                const float4 v = make_float4(pg[0], pg[1], pg[2], pg[3]);
-                if (rr < nv) st4(dz1_out + (s * SM + rr) * 64 + 4 * c4, v);
-            }
-        }
-        if (dims) zero_pad(s, nv);
-        nv = next_nv;
-    }
-    SCGIB_MARK(5);
-    if constexpr (!WG) return;
-    // per-workgroup slab: dW2 [64][64] | db2 [64] | db1 [64]
-    float *sl = slab + static_cast<int64_t>(blockIdx.x) * kZSlab;
-    if (!nw) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int j = q * 32 + acc_row(reg, l);
-            sl[j * 64 + li] = accA[reg];
-            sl[j * 64 + 32 + li] = accB[reg];
-        }
-    }
-    dbias += __shfl_xor(dbias, 32, kWave);
-    if (l < 32) sl[64 * 64 + (nw ? 64 : 0) + q * 32 + l] = dbias;
-    SCGIB_MARK(6);
-}
+}  // namespace scgib
+#include "gin_bwd5.h"  // gin_bwd5_k, gin_bwd5z_k, gin_bwd5r_k
+namespace scgib {
 
 // gin_bwd_statsz_k: the backward statistics of layer l below an agg-free layer
 // l + 1 — gin_bwd_stats_k<GATHER>'s work with the transposed gather taken over
@@ -2195,285 +1366,6 @@ __global__ __launch_bounds__(256, 2) void gin_bwd_statsz_k(
             sl[(32 * rw + acc_row(reg, l)) * 64 + 32 * cq + li] = sG[threadIdx.x * 16 + reg];
     }
     SCGIB_MARK(4);
-}
-
-// ---------------------------------------------------------------------------
-// gin_bwd5r_k: gin_bwd5_k without the saved r.  The
-// forward no longer writes r = relu(agg W1^T + b1) — one of the three [N,64]
-// row sets gin_fwd_k stored, a third of its HBM writes — and this kernel
-// recomputes it per sub-tile from the agg rows it stages anyway, with the
-// forward's own MFMA chain (v_mfma_f32_32x32x2_f32, step s = k pair (2 s,
-// 2 s + 1), s = 0..31 in order from zero, then + b1 and fmaxf 0), so every r
-// element is bitwise the one the forward would have stored; every other
-// product is one of gin_bwd5_k's chains unchanged (same operands, same order
-// per output element), so dW1 / dW2 / db / d(agg) are bitwise gin_bwd5_k's
-// (tests/test_gpu_parity.py::test_gin_layer_bwd_recompute_bitwise).
-// Roles, 80 MFMAs per wave and sub-tile (gin_bwd5_k: 64) in three phases:
-//   1: waves 0,1: r block q = agg W1[32q.., :]^T + b1, relu -> r^T image
-//                 (and the block's ReLU mask, 16 bits in one register)
-//      waves 2,3: dr block q = dz2 W2[:, 32q..] -> the dz1^T image
-//   2: waves 0,1: dz1 = dr [r > 0] (their own block) -> dz1 / dz1^T images
-//      every wave: dW2 block (q, w >> 1) += dz2^T r (db2: waves 0,1)
-//   3: waves 0,1: d(agg) block q = dz1 W1[:, 32q..] -> staging
-//      waves 2,3: dW1 rows 32q.. += dz1^T agg (db1)
-//   (+ the next sub-tile's dz2 staged during phase 3: three barriers)
-// Registers: waves 0,1 hold W1 rows (r) and W1 columns (d(agg)), waves 2,3
-// W2 columns (dr) and two dW1 accumulators — the second weight block and
-// those accumulators are the same two f32x16.  LDS: gin_bwd5_k's images
-// (r^T now written by phase 1) + the agg rows with each row's k split
-// even | odd (lane half kk reads k = 2 s + kk, s = 0..31, as one run: b128
-// operand reads) = 72 KB, two workgroups per CU.
-// ---------------------------------------------------------------------------
-constexpr int kEO = 32;  // even | odd split: k -> (k & 1) * 32 + (k >> 1)
-
-template <int DIN>
-__global__ __launch_bounds__(256, 2) void gin_bwd5r_k(
-    const float *__restrict__ dy, const float *__restrict__ z2, const float *__restrict__ agg,
-    const float *__restrict__ stat, const float *__restrict__ coef, const float *__restrict__ w1,
-    const float *__restrict__ b1, const float *__restrict__ w2, int64_t ncap, int64_t nsub,
-    float *__restrict__ dagg_out, float *__restrict__ slab, const int32_t *__restrict__ dims,
-    scgib_bn_bwd_pending pend) {
-    static_assert(DIN == 64 && SM == 32, "64-wide rows, 32-row sub-tiles");
-    constexpr int SLAB = 64 * 64 + 64 * DIN + 128;
-    __shared__ __attribute__((aligned(16))) float sD[SM * LDR];   // dz2 [row][k]
-    __shared__ __attribute__((aligned(16))) float sDT[64 * LDT];  // dz2 [col][row]
-    __shared__ __attribute__((aligned(16))) float sE[SM * LDR];   // dz1
-    __shared__ __attribute__((aligned(16))) float sET[64 * LDT];
-    __shared__ __attribute__((aligned(16))) float sRT[64 * LDT];  // r [col][row] (recomputed)
-    __shared__ __attribute__((aligned(16))) float sAT[DIN * LDT]; // agg [col][row]
-    __shared__ __attribute__((aligned(16))) float sAR[SM * LDR];  // agg [row][even | odd k]
-    __shared__ float sG[SM * LDH];                                 // d(agg) staging
-    __shared__ float sCoef[128];
-    const int64_t n = eff_count(dims, 0, ncap);
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
-    const int kk = l >> 5, li = l & 31;
-    const bool ra = w < 2;  // wave-uniform role: r, d(agg) (waves 0,1) or dr, dW1 (2,3)
-    const int q = w & 1;    // the role's 32-wide block
-    const int c = l;        // elementwise: column c, rows 8 w .. 8 w + 7
-    const int64_t last = ncap - 1;
-    const int64_t G = gridDim.x;
-    SCGIB_MARK(0);
-    SCGIB_MARK_HWID();
-    BwdFin bfin;
-    const int pend_ngr = static_cast<int>(((n + TM - 1) / TM + kGroup - 1) / kGroup);
-    if (pend.gpart) bn_bwd_fin_load<false>(pend.gpart, pend_ngr, 0, bfin);
-    const float s_mean = stat[c], s_istd = stat[64 + c], s_sc = stat[128 + c];
-    float c1 = 0.f, c2 = 0.f;
-    if (!pend.gpart) {
-        c1 = coef[c];
-        c2 = coef[64 + c];
-    }
-    // wa: waves 0,1 W1[32q + li][2 s + kk] (r, the forward's k order);
-    //     waves 2,3 W2[kperm(s, kk)][32q + li] (dr)
-    // X0 | X1: waves 0,1 W1[kperm(s, kk)][32q + li] (d(agg));
-    //          waves 2,3 the dW1 accumulators (q, 0) | (q, 1)
-    float wa[32];
-    f32x16 X0 = zero16(), X1 = zero16();
-    float bias1 = 0.f;
-    if (ra) {
-#pragma unroll
-        for (int s = 0; s < 32; ++s) wa[s] = w1[(q * 32 + li) * DIN + 2 * s + kk];
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            X0[s] = w1[kperm(s, kk) * DIN + q * 32 + li];
-            X1[s] = w1[kperm(s + 16, kk) * DIN + q * 32 + li];
-        }
-        bias1 = b1[q * 32 + li];
-    } else {
-#pragma unroll
-        for (int s = 0; s < 32; ++s) wa[s] = w2[kperm(s, kk) * 64 + q * 32 + li];
-    }
-    // a sub-tile's column c, rows 8 w + i: [0] dy, [1] z2, [2] agg.  The next
-    // sub-tile's agg rows are loaded a whole sub-tile ahead (its r^T / agg
-    // images are written after this one's barriers 1 and 3), its dy / z2 only
-    // after barrier 1 (staged in phase 3): fewer registers live across phase 1
-    float nx[3][8];
-    auto load_agg = [&](int64_t s) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            int64_t row = s * SM + 8 * w + i;
-            row = row < last ? row : last;
-            nx[2][i] = agg[row * DIN + c];
-        }
-    };
-    auto load_dz = [&](int64_t s) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            int64_t row = s * SM + 8 * w + i;
-            row = row < last ? row : last;
-            nx[0][i] = dy[row * 64 + c];
-            nx[1][i] = z2[row * 64 + c];
-        }
-    };
-    auto load_sub = [&](int64_t s) {
-        load_agg(s);
-        load_dz(s);
-    };
-    auto put_at = [&]() {  // agg column c, rows 8w..8w+7 -> [c][row]
-        float4 *p = reinterpret_cast<float4 *>(sAT + c * LDT + 8 * w);
-        p[0] = make_float4(nx[2][0], nx[2][1], nx[2][2], nx[2][3]);
-        p[1] = make_float4(nx[2][4], nx[2][5], nx[2][6], nx[2][7]);
-    };
-    auto put_ar = [&]() {  // agg column c -> position (c & 1) * 32 + (c >> 1) of rows 8w..
-        const int pos = (c & 1) * kEO + (c >> 1);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sAR[(8 * w + i) * LDR + pos] = nx[2][i];
-    };
-    auto rows_of = [&](int64_t s) {
-        const int64_t v = n - s * SM;
-        return static_cast<int>(v < SM ? (v > 0 ? v : 0) : SM);
-    };
-    auto zero_pad = [&](int64_t s, int from) {
-        const int64_t row0 = s * SM;
-        const int ncr = static_cast<int>(ncap - row0 < SM ? ncap - row0 : SM);
-        for (int idx = from * DIN + tid; idx < ncr * DIN; idx += 256) dagg_out[row0 * DIN + idx] = 0.f;
-    };
-    float k1 = 0.f;
-    // dz2 = sc (dy - c1 - (z2 - mean) istd c2), rows past nv zero -> sD, sDT
-    auto stage_dz2 = [&](int nvs) {
-        float d[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float v = s_sc * (nx[0][i] - c1 - (nx[1][i] - s_mean) * k1);
-            d[i] = 8 * w + i < nvs ? v : 0.f;
-            sD[(8 * w + i) * LDR + c] = d[i];
-        }
-        float4 *p = reinterpret_cast<float4 *>(sDT + c * LDT + 8 * w);
-        p[0] = make_float4(d[0], d[1], d[2], d[3]);
-        p[1] = make_float4(d[4], d[5], d[6], d[7]);
-    };
-    int64_t s = blockIdx.x;
-    int nv = s < nsub ? rows_of(s) : 0;
-    if (nv > 0) load_sub(s);
-    if (pend.gpart) {  // finish the BN-backward sums; workgroup 0 writes dgamma, dbeta
-        const double tot = bn_bwd_final<false>(pend.gpart, pend_ngr, bfin);
-        const int cs = bfin_index();
-        const bool lead = (tid & 63) < 32, w0 = blockIdx.x == 0 && lead;
-        const float cf = bn_bwd_publish(cs, tot, n, pend.training, w0 ? pend.dgamma : nullptr,
-                                        w0 ? pend.dbeta : nullptr, nullptr);
-        if (lead) sCoef[cs] = cf;
-        __syncthreads();
-        c1 = sCoef[c];
-        c2 = sCoef[64 + c];
-    }
-    k1 = s_istd * c2;
-    if (nv > 0) {
-        put_at();
-        put_ar();
-        stage_dz2(nv);
-    }
-    // the weight registers complete here (see gin_bwd5_k)
-    vm_wait_all();
-    __syncthreads();
-    // the second sub-tile's agg rows: in flight during the first one's phase 1
-    if (nv > 0 && s + G < nsub && rows_of(s + G) > 0) load_agg(s + G);
-    SCGIB_MARK(1);
-    f32x16 acc0 = zero16();  // waves 0,1: dW2 block (q, 0); waves 2,3: dW2 block (q, 1)
-    float dbias = 0.f;       // waves 0,1: db2 [32q + li]; waves 2,3: db1
-    for (int it = 0; s < nsub; s += G, ++it) {
-        if (nv == 0) {  // capacity tail: this and every later sub-tile is padding
-            for (int64_t t = s; t < nsub; t += G) zero_pad(t, rows_of(t));
-            break;
-        }
-        const int64_t next = s + G;
-        const int next_nv = next < nsub ? rows_of(next) : 0;  // block-uniform
-        // the element (row 8 g + 4 kk + t, column 32 q + li) of block q sits in
-        // register 4 g + t of every role: one b128 per g in the [col][row] images
-        const int col = q * 32 + li;
-        unsigned rmask = 0u;  // waves 0,1: bit 4 g + t = [r > 0] of their r block
-        if (ra) {  // phase 1: r block q (the forward's chain), relu -> sRT as [col][row]
-            const f32x16 z = mma_rk4<8, 4>(sAR + li * LDR + kk * kEO, wa, zero16());
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float v[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    v[t] = fmaxf(z[4 * g + t] + bias1, 0.f);
-                    rmask |= (v[t] > 0.f ? 1u : 0u) << (4 * g + t);
-                }
-                *reinterpret_cast<float4 *>(sRT + col * LDT + 8 * g + 4 * kk) = make_float4(v[0], v[1], v[2], v[3]);
-            }
-        } else {   // phase 1: dr block q -> sET [col][row] (masked in phase 2 by waves 0,1)
-            const f32x16 dr = mma_rk4<8>(sD + li * LDR + 4 * kk, wa, zero16());
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4 *>(sET + col * LDT + 8 * g + 4 * kk) =
-                    make_float4(dr[4 * g], dr[4 * g + 1], dr[4 * g + 2], dr[4 * g + 3]);
-        }
-        lds_barrier();  // r^T and dr complete; the agg rows consumed
-        if (it == 0) SCGIB_MARK(2);
-        if (next_nv > 0) {
-            put_ar();
-            load_dz(next);  // staged in phase 3
-        }
-        if (ra) {  // phase 2: dz1 = dr [r > 0] -> sE, sET in place (mask by multiplication)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float4 *pt = reinterpret_cast<float4 *>(sET + col * LDT + 8 * g + 4 * kk);
-                const float4 d = *pt;
-                const float4 v = make_float4(d.x * ((rmask >> (4 * g)) & 1u ? 1.f : 0.f),
-                                             d.y * ((rmask >> (4 * g + 1)) & 1u ? 1.f : 0.f),
-                                             d.z * ((rmask >> (4 * g + 2)) & 1u ? 1.f : 0.f),
-                                             d.w * ((rmask >> (4 * g + 3)) & 1u ? 1.f : 0.f));
-                const int row = 8 * g + 4 * kk;
-                sE[row * LDR + col] = v.x;
-                sE[(row + 1) * LDR + col] = v.y;
-                sE[(row + 2) * LDR + col] = v.z;
-                sE[(row + 3) * LDR + col] = v.w;
-                *pt = v;
-            }
-        }
-        // phase 2: dW2 rows 32q.., columns 32 (w >> 1).. += dz2^T r (db2 on waves 0,1)
-        if (ra)
-            mma_kk4<4, true>(sDT + (q * 32 + li) * LDT + 4 * kk, sRT + li * LDT + 4 * kk, acc0, dbias);
-        else
-            mma_kk4<4, false>(sDT + (q * 32 + li) * LDT + 4 * kk, sRT + (32 + li) * LDT + 4 * kk, acc0, dbias);
-        lds_barrier();  // dz1 complete; dz2 and r consumed
-        if (it == 0) SCGIB_MARK(3);
-        if (ra) {  // phase 3: d(agg) block q = dz1 W1[:, 32q..] -> staging
-            const f32x16 da = mma_rk4<8>(sE + li * LDR + 4 * kk, W32{X0, X1}, zero16());
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) sG[acc_row(reg, l) * LDH + q * 32 + li] = da[reg];
-        } else {   // phase 3: dW1 rows 32q.. += dz1^T agg (db1 from the A operand)
-            mma_kk4x2<4>(sET + (q * 32 + li) * LDT + 4 * kk, sAT + li * LDT + 4 * kk,
-                         sAT + (32 + li) * LDT + 4 * kk, X0, X1, dbias);
-        }
-        if (next_nv > 0) stage_dz2(next_nv);  // dz2 and its images are free since the barrier
-        lds_barrier();  // d(agg) staged, next dz2 staged; agg^T and dz1 consumed
-        if (it == 0) SCGIB_MARK(4);
-        if (next_nv > 0) {
-            put_at();
-            const int64_t nn = next + G;  // the sub-tile after: in flight during the next one
-            if (nn < nsub && rows_of(nn) > 0) load_agg(nn);
-        }
-        {   // d(agg) rows: full-row float4 stores (after the loads: in-order vmcnt)
-            const int c4 = tid & 15, rs = tid >> 4;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int rr = rs + 16 * k;
-                const float *pg = sG + rr * LDH + 4 * c4;
-                const float4 v = make_float4(pg[0], pg[1], pg[2], pg[3]);
-                if (rr < nv) st4(dagg_out + (s * SM + rr) * DIN + 4 * c4, v);
-            }
-        }
-        if (dims) zero_pad(s, nv);
-        nv = next_nv;
-    }
-    SCGIB_MARK(5);
-    // per-workgroup slab: dW2 | dW1 | db2 | db1 (gin_bwd_k layout)
-    float *sl = slab + static_cast<int64_t>(blockIdx.x) * SLAB;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int j = q * 32 + acc_row(reg, l);
-        sl[j * 64 + (ra ? 0 : 32) + li] = acc0[reg];
-        if (!ra) {
-            sl[64 * 64 + j * DIN + li] = X0[reg];
-            sl[64 * 64 + j * DIN + 32 + li] = X1[reg];
-        }
-    }
-    dbias += __shfl_xor(dbias, 32, kWave);
-    if (l < 32) sl[64 * 64 + 64 * DIN + (ra ? 0 : 64) + q * 32 + l] = dbias;
-    SCGIB_MARK(6);
 }
 
 // up to two workgroups per CU (66.5 KB LDS each): one tile per workgroup for

@@ -995,14 +995,24 @@ def test_gin_encoder_transfer_fold_small_exact(pkg, dev, via_ego):
     assert rel_l2(gw.cpu(), gw64) < 1e-5
 
 
+@pytest.mark.parametrize("path", ["stored", "agg_free", "recompute"])
 @pytest.mark.parametrize("via_ego,n_mols", [(False, 40), (True, 200)])
-def test_gin_encoder_deferred_bn_bitwise(pkg, dev, via_ego, n_mols):
+def test_gin_encoder_deferred_bn_bitwise(pkg, dev, via_ego, n_mols, path, monkeypatch):
     """Deferred BatchNorm finalize (scgib_bn_pending: the next kernel finishes
     a layer's statistics) against the in-kernel last-arriver finalize: both
     run the same fixed-order combine, so outputs, every gradient and the BN
     running statistics are bitwise identical; n_mols = 200 ego-nets spans
-    several 16-tile groups with a partial last group."""
+    several 16-tile groups with a partial last group.  path: the d = 64 layer
+    backward that consumes the coefficients either way — gin_bwd5_k (stored:
+    the defaults at these sizes), gin_bwd5z_k (agg_free) or gin_bwd5r_k
+    (recompute)."""
     import copy
+    if path == "agg_free":
+        monkeypatch.setattr(pkg.ops, "AGG_FREE", True)
+        monkeypatch.setattr(pkg.ops, "AGG_FREE_MIN_ROWS", 0)
+    elif path == "recompute":
+        monkeypatch.setattr(pkg.ops, "STORE_R", False)
+        monkeypatch.setattr(pkg.ops, "AGG_FREE", False)
     torch.manual_seed(5)
     g, _ = rand_graph(pkg, n_mols, "qm9", 12, dev)
     x = F.normalize(torch.rand(g.num_nodes(), 11)).to(dev)
