@@ -1096,6 +1096,46 @@ int scgib_grad_pack(const scgib_grad_slice *tensors, int32_t n_tensors, float *f
                     scgib_stream_t stream);
 int scgib_grad_unpack(const scgib_grad_slice *tensors, int32_t n_tensors, const float *flat,
                       float scale, scgib_stream_t stream);
+
+/* ---- evaluation metrics on the device (csrc/eval_metrics.hip)
+ * metrics.py:18-87 (eval_rocauc / eval_ap / eval_rmse / eval_acc: per task
+ * column, NaN labels left out) and the score concatenation of the loops
+ * (train_molpcba.py:156-159, :165-207), without a host copy.
+ *
+ * scgib_eval_append: copies scores / targets [n_rows][n_tasks] to row state[0]
+ *   of buf_scores / buf_labels [capacity][n_tasks] and advances state[0] (the
+ *   launch's last workgroup does, so a captured launch appends on every
+ *   replay).  state: three uint32 — the row cursor, an arrival counter (zero on
+ *   entry, left zero) and the error word.  Rows that would pass `capacity` are
+ *   not written; the cursor then stops at `capacity` and error bit 1 is set.
+ * scgib_eval_keys: tasks [task0, task0 + n_group) of the row-major scores /
+ *   labels [n_rows][n_tasks] -> task-major keys [n_group][n_rows] (int64):
+ *   ((~o(score)) << 1) | label, o the order-preserving uint32 image of the
+ *   fp32 score (-0.0 as +0.0), so ascending keys are descending scores with
+ *   the label in bit 0; an element whose label is not 0 or 1, and every row at
+ *   or past *rows (device uint32, NULL: n_rows), gets INT64_MAX.  Per row tile
+ *   t < scgib_eval_tiles(n_rows) and task c it writes sq_slab[t][c] (fp64
+ *   squared error over the labelled elements) and cnt_slab[t][c][4] (labels
+ *   equal to 1, equal to 0, not NaN, equal to their score).  Error bits OR-ed
+ *   into *err: 2 a NaN score under a label that is not NaN, 4 a label that is
+ *   neither 0, 1 nor NaN.
+ * scgib_eval_scan: `sorted` = the keys sorted ascending along each row (any
+ *   sort; only values).  Writes out[4][n_tasks] (fp64: ROC-AUC, average
+ *   precision, RMSE, accuracy; NaN where undefined — a rank metric of a task
+ *   without both classes, RMSE / accuracy of a task without labelled rows)
+ *   and counts[3][n_tasks] (int32: labels 1, labels 0, labelled) for the
+ *   group's tasks.  Integer sums are exact, fp64 sums have a fixed order:
+ *   bitwise reproducible, and independent of how the tasks are grouped. */
+int64_t scgib_eval_tiles(int64_t n_rows);
+int scgib_eval_append(const float *scores, const float *targets, int64_t n_rows, int32_t n_tasks,
+                      float *buf_scores, float *buf_labels, int64_t capacity, uint32_t *state,
+                      scgib_stream_t stream);
+int scgib_eval_keys(const float *scores, const float *labels, int64_t n_rows, int32_t n_tasks,
+                    int32_t task0, int32_t n_group, const uint32_t *rows, int64_t *keys,
+                    double *sq_slab, int32_t *cnt_slab, uint32_t *err, scgib_stream_t stream);
+int scgib_eval_scan(const int64_t *sorted, int64_t n_rows, int32_t n_tasks, int32_t task0,
+                    int32_t n_group, const double *sq_slab, const int32_t *cnt_slab, double *out,
+                    int32_t *counts, scgib_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

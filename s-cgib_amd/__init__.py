@@ -14,7 +14,8 @@ Layout:
                (Transformer, GraphTransformerLayer and MultiHeadAttentionLayer are
                also attributes of the package)
   metric_wrapper.py  MetricWrapper.py-compatible MetricWrapper (NaN-masked losses on the device)
-  metrics.py   ROC-AUC (OGB semantics) and TU accuracy of the fine-tune configs
+  metrics.py   ROC-AUC (OGB semantics) and TU accuracy of the fine-tune configs; EvalBuffer,
+               the device-side score buffer and metrics of an epoch (also a package attribute)
   optim.py     one-launch device Adam (drop-in for torch.optim.Adam as the scripts use it)
   cache.py     on-disk CSR cache of a molecule dataset (replaces the pts/ pickles)
   refckpt.py   the reference's whole-module checkpoints, read weights-only
@@ -34,6 +35,8 @@ _MODEL_NAMES = ("Transformer", "GraphTransformerLayer", "MultiHeadAttentionLayer
 def __getattr__(name):
     if name == "MetricWrapper":
         return importlib.import_module(f"{__name__}.metric_wrapper").MetricWrapper
+    if name == "EvalBuffer":
+        return importlib.import_module(f"{__name__}.metrics").EvalBuffer
     if name in _MODEL_NAMES:
         return getattr(importlib.import_module(f"{__name__}.models"), name)
     if name in __all__:

@@ -189,6 +189,10 @@ SIGNATURES = {
     "scgib_adam_step": (ctypes.c_int, [_P, _I32, _D, _D, _D, _D, _D, _P, _P]),
     "scgib_adam_reduce_max_jobs": (_I64, []),
     "scgib_adam_step_reduce": (ctypes.c_int, [_P, _I32, _P, _I32, _D, _D, _D, _D, _D, _P, _P]),
+    "scgib_eval_tiles": (_I64, [_I64]),
+    "scgib_eval_append": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I64, _P, _P]),
+    "scgib_eval_keys": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "scgib_eval_scan": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
 }
 
 

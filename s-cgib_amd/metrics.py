@@ -91,3 +91,100 @@ def accuracy_TU(scores, targets):
 
 def MAE(scores, targets):
     return torch.nn.functional.l1_loss(scores, targets).detach().item()
+
+
+class EvalBuffer:
+    """Device-side score buffer and metrics of an evaluation epoch.
+
+    Replaces the loops' ``scores = torch.cat((scores, batch_scores))`` and the
+    host evaluator (train_molpcba.py:156-159, :165-207): ``append`` is one HIP
+    launch that copies the batch to a device row cursor and advances it — no
+    synchronisation, no allocation, so it captures into ``torch.cuda.graph`` /
+    the replayed fine-tune step, and every replay appends the batch that is in
+    the static inputs at that moment.  The metrics are computed on the device
+    (ops.rank_metrics) with the semantics of eval_rocauc / eval_ap / eval_rmse /
+    eval_acc; an epoch ends with the single synchronisation of a scalar method.
+
+    ``capacity`` counts stored rows.  Rows whose labels are all NaN are stored
+    like any other row and ignored by every metric; capacity mode's padded
+    molecules are such rows, so size ``capacity`` in padded rows (steps x
+    batch capacity), not in molecules.  Rows that would pass ``capacity`` are
+    dropped, the cursor stops there and the next scalar method raises.
+    """
+
+    def __init__(self, capacity, num_tasks, device, workspace_bytes=256 << 20):
+        from . import _lib
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.ScgibError(f"EvalBuffer: device {device}; the evaluation buffer lives on the "
+                                  "HIP device only (no CPU fallback)")
+        capacity, num_tasks = int(capacity), int(num_tasks)
+        if capacity < 1 or num_tasks < 1 or capacity > 0x7fffffff:
+            raise _lib.ScgibError(f"EvalBuffer: capacity {capacity} x {num_tasks} tasks")
+        self.capacity, self.num_tasks = capacity, num_tasks
+        self.workspace_bytes = int(workspace_bytes)
+        self.scores = torch.empty(capacity, num_tasks, dtype=torch.float32, device=device)
+        self.labels = torch.empty(capacity, num_tasks, dtype=torch.float32, device=device)
+        # cursor, arrival counter of append's launch, error word, spare
+        self.state = torch.zeros(4, dtype=torch.int32, device=device)
+
+    def append(self, scores, targets):
+        """Store the [B, C] batch (fp32, or anything ops._f32 converts) at the
+        cursor; asynchronous and capturable."""
+        from . import ops
+        ops.eval_append(scores, targets, self.scores, self.labels, self.state)
+
+    def reset(self):
+        """Cursor and error word back to zero (a device memset; capturable)."""
+        self.state.zero_()
+
+    def rows(self):
+        """Rows stored so far.  Synchronises: for use outside the loop."""
+        return int(self.state[0].item())
+
+    def per_task(self):
+        """Device tensors ``auc, ap, rmse, acc`` (fp64 [C]) and ``pos, neg``
+        (int32 [C]) over the stored rows, without synchronising (also
+        ``labelled`` and the error word ``err``)."""
+        from . import ops
+        return ops.rank_metrics(self.scores, self.labels, rows=self.state[0:1],
+                                err=self.state[2:3], workspace_bytes=self.workspace_bytes)
+
+    def _read(self, ignore=0):
+        """per_task() and its one read: numpy [7, C] (auc, ap, rmse, acc, pos,
+        neg, labelled); raises on the error word's bits outside ``ignore``."""
+        from . import _lib, ops
+        r = self.per_task()
+        flat = torch.cat([torch.stack([r["auc"], r["ap"], r["rmse"], r["acc"]]).flatten(),
+                          torch.stack([r["pos"], r["neg"], r["labelled"]]).flatten().double(),
+                          r["err"].double()]).cpu().numpy()
+        bits = int(flat[-1]) & ~ignore
+        if bits:
+            names = "; ".join(text for bit, text in ops.EVAL_ERR_NAMES if bits & bit)
+            raise _lib.ScgibError(f"EvalBuffer: {names} (error word {bits})")
+        return flat[:-1].reshape(7, self.num_tasks)
+
+    def _rank_mean(self, row, what):
+        t = self._read()
+        vals = [float(v) for v, p, n in zip(t[row], t[4], t[5]) if p > 0 and n > 0]
+        if not vals:
+            raise RuntimeError(f"No positively labeled data available. Cannot compute {what}.")
+        return sum(vals) / len(vals)
+
+    def rocauc(self):
+        return {"rocauc": self._rank_mean(0, "ROC-AUC")}
+
+    def ap(self):
+        return self._rank_mean(1, "Average Precision")
+
+    def rmse(self):
+        from . import ops
+        t = self._read(ignore=ops.EVAL_ERR_LABEL)
+        return {"rmse": sum(float(v) for v in t[2]) / self.num_tasks}
+
+    def acc(self):
+        from . import ops
+        t = self._read(ignore=ops.EVAL_ERR_LABEL)
+        if (t[6] == 0).any():
+            raise ZeroDivisionError("float division by zero")
+        return {"acc": sum(float(v) for v in t[3]) / self.num_tasks}

@@ -2828,3 +2828,101 @@ def gt_encoder(h, graph, module, drop_masks=None):
     for i, layer in enumerate(module.layers):
         h = gt_layer(h, graph, layer, None if drop_masks is None else drop_masks[i])
     return h
+
+
+# ---------------------------------------------------------------------------
+# Evaluation metrics on the device (csrc/eval_metrics.hip)
+# ---------------------------------------------------------------------------
+EVAL_ERR_OVERFLOW = 1   # an append passed the buffer's capacity
+EVAL_ERR_NAN_SCORE = 2  # a NaN score on a labelled element
+EVAL_ERR_LABEL = 4      # a label that is neither 0, 1 nor NaN (rank metrics only)
+EVAL_ERR_NAMES = ((EVAL_ERR_OVERFLOW, "overflow: rows were appended past the capacity"),
+                  (EVAL_ERR_NAN_SCORE, "a NaN score on a labelled element"),
+                  (EVAL_ERR_LABEL, "a label that is neither 0, 1 nor NaN"))
+# workspace per (row, task) element: the key, and torch.sort's two outputs
+EVAL_ELEMENT_BYTES = 24
+
+
+def _eval_pair(name, scores, targets):
+    scores, targets = _f32(scores, name), _f32(targets, name)
+    if scores.dim() == 1:
+        scores = scores[:, None]
+    if targets.dim() == 1:
+        targets = targets[:, None]
+    if scores.dim() != 2 or scores.shape != targets.shape or scores.shape[1] < 1:
+        raise _lib.ScgibError(f"{name}: scores {tuple(scores.shape)} and targets "
+                              f"{tuple(targets.shape)} must be the same [rows, tasks]")
+    return scores, targets
+
+
+def eval_append(scores, targets, buf_scores, buf_labels, state):
+    """Append the [B, C] batch to the fp32 buffers [capacity, C] at the device
+    row cursor ``state[0]`` (int32 [4]: cursor, arrival counter, error word,
+    spare) in one launch on the current stream; no synchronisation, so it
+    captures into a replayed step (metrics.EvalBuffer.append)."""
+    scores, targets = _eval_pair("eval_append", scores, targets)
+    cap, c = buf_scores.shape
+    if (scores.shape[1] != c or buf_labels.shape != buf_scores.shape or not buf_scores.is_cuda
+            or buf_scores.dtype != torch.float32 or buf_labels.dtype != torch.float32
+            or not buf_scores.is_contiguous() or not buf_labels.is_contiguous()
+            or state.dtype != torch.int32 or state.numel() < 3 or not state.is_cuda):
+        raise _lib.ScgibError("eval_append: the batch does not fit the buffers "
+                              f"(batch {tuple(scores.shape)}, buffers {tuple(buf_scores.shape)})")
+    _lib.call("scgib_eval_append", _p(scores), _p(targets), scores.shape[0], c, _p(buf_scores),
+              _p(buf_labels), cap, _p(state), _stream())
+
+
+def rank_metrics(scores, targets, rows=None, err=None, workspace_bytes=256 << 20, marks=None):
+    """Per-task ROC-AUC, average precision, RMSE and accuracy of device scores
+    against device targets [n, C] (NaN target = unlabelled), with the
+    semantics of metrics.eval_rocauc / eval_ap / eval_rmse / eval_acc per task.
+
+    Returns a dict of device tensors and does not synchronise: ``auc``, ``ap``,
+    ``rmse``, ``acc`` (fp64 [C]; NaN where the task has not both classes, or no
+    labelled row), ``pos``, ``neg``, ``labelled`` (int32 [C]) and ``err`` (int32
+    [1], EVAL_ERR_* bits).  ``rows``: device int32 [1] with the live row count
+    (rows at or past it are ignored); ``err``: an error word to OR into.
+
+    Pipeline per group of tasks: key build (HIP) -> torch.sort of the packed
+    keys, values only in use (library primitive) -> tie-group scan (HIP).  The
+    groups keep keys plus sort outputs under ``workspace_bytes``; the result
+    does not depend on the grouping, bit for bit.  ``marks``: a list that
+    receives (phase, event) pairs for timing (tools/eval_bench.py)."""
+    scores, targets = _eval_pair("rank_metrics", scores, targets)
+    n, c = scores.shape
+    if n < 1:
+        raise _lib.ScgibError("rank_metrics: no rows")
+    dev = scores.device
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    for name, t in (("rows", rows), ("err", err)):
+        if t is not None and (not t.is_cuda or t.dtype != torch.int32 or t.numel() < 1):
+            raise _lib.ScgibError(f"rank_metrics: {name} must be an int32 tensor on the HIP device")
+    tiles = _lib.query("scgib_eval_tiles", n)
+    sq_slab = torch.empty(tiles * c, dtype=torch.float64, device=dev)
+    cnt_slab = torch.empty(tiles * c * 4, dtype=torch.int32, device=dev)
+    out = torch.empty(4, c, dtype=torch.float64, device=dev)
+    counts = torch.empty(3, c, dtype=torch.int32, device=dev)
+    group = int(max(1, min(c, int(workspace_bytes) // (EVAL_ELEMENT_BYTES * n))))
+    keys = torch.empty(group, n, dtype=torch.int64, device=dev)
+    st = _stream()
+
+    def mark(phase):
+        if marks is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            marks.append((phase, ev))
+
+    mark("start")
+    for c0 in range(0, c, group):
+        ng = min(group, c - c0)
+        _lib.call("scgib_eval_keys", _p(scores), _p(targets), n, c, c0, ng, _p(rows), _p(keys),
+                  _p(sq_slab), _p(cnt_slab), _p(err), st)
+        mark("keys")
+        ordered = torch.sort(keys[:ng], dim=1).values
+        mark("sort")
+        _lib.call("scgib_eval_scan", _p(ordered), n, c, c0, ng, _p(sq_slab), _p(cnt_slab),
+                  _p(out), _p(counts), st)
+        mark("scan")
+    return {"auc": out[0], "ap": out[1], "rmse": out[2], "acc": out[3], "pos": counts[0],
+            "neg": counts[1], "labelled": counts[2], "err": err}
