@@ -1136,6 +1136,59 @@ int scgib_eval_keys(const float *scores, const float *labels, int64_t n_rows, in
 int scgib_eval_scan(const int64_t *sorted, int64_t n_rows, int32_t n_tasks, int32_t task0,
                     int32_t n_group, const double *sq_slab, const int32_t *cnt_slab, double *out,
                     int32_t *counts, scgib_stream_t stream);
+
+/* Device-side collation of shuffled batches from a resident dataset
+ * (collate.hip; graph.DeviceDataset / graph.DeviceLoader).
+ * Entry points only: the ABI version does not change.
+ *
+ * The dataset: M molecules as flat arrays — node_off / edge_off [M+1] (64-bit
+ * offsets of each molecule's nodes and edges), rp_local [nodes] (row pointer
+ * of each node inside its molecule's edge range), col [edges] (molecule-local
+ * source ids, dst-major CSR), x [nodes][F], y [M][T] (T = 0: none),
+ * ego_nodes / ego_edges [M] (the molecule's k-hop ego bounds).
+ * The sequence: perm [2][M] holds the permutations of epochs of even and odd
+ * number; state[0] is the position j in [0, 2S) (S batches of B per epoch),
+ * state[1] the sticky count of batches that did not fit.  Batch j is
+ * perm[j / S][(j % S) * B .. + B).
+ * The ring: srcs = table of three slot pointers, each blob_bytes long in
+ * StaticBatch's layout (sections rowptr [n_cap+1], col [max(e_cap,1)],
+ * graph_ptr [B+1], dims [4], x [n_cap][F] at the byte offsets o_*, multiples
+ * of 16); cursor = the pool cursor scgib_pool_copy advances.
+ *
+ * scgib_collate_plan (one workgroup, B <= scgib_collate_max_batch()): the ids
+ *   of batch state[0] + ahead, their node / edge offsets into ws (int32,
+ *   scgib_collate_ws_words(B)) and, when the batch fits n_cap, e_cap and the
+ *   ego capacities, into slot_ids [3][B] at the destination slot: `slot` in
+ *   0..2, or -1 = (cursor[0] + 1) % 3.  Else state[1] is bumped.  advance:
+ *   state[0] moves on by one.
+ * scgib_collate_fill: writes the planned batch into its slot — every byte of
+ *   the five sections, tails as StaticBatch.pad writes them — or nothing when
+ *   the plan found it not to fit; labels != 0: also gathers the labels [B][T]
+ *   and ids [B] of the batch in slot (cursor[0] + 2) % 3 (the one the step's
+ *   scgib_pool_copy read) as the plan saw the cursor. */
+typedef struct {
+    const int64_t *node_off, *edge_off;
+    const int32_t *rp_local, *col;
+    const float *x, *y;
+    const int32_t *ego_nodes, *ego_edges;
+    const int32_t *perm;
+    const uint64_t *srcs;
+    const uint32_t *cursor;
+    uint32_t *state;
+    int32_t *ws;
+    int32_t *slot_ids;
+    float *labels;
+    int32_t *ids;
+    int64_t M, S;
+    int64_t n_cap, e_cap, ego_n_cap, ego_e_cap;
+    int64_t o_rowptr, o_col, o_gptr, o_dims, o_x, blob_bytes;
+    int32_t B, F, T, pad_;
+} scgib_collate_desc;
+int64_t scgib_collate_max_batch(void);
+int64_t scgib_collate_ws_words(int64_t batch);
+int scgib_collate_plan(const scgib_collate_desc *d, int32_t ahead, int32_t slot, int32_t advance,
+                       scgib_stream_t stream);
+int scgib_collate_fill(const scgib_collate_desc *d, int32_t labels, scgib_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

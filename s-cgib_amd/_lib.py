@@ -193,6 +193,10 @@ SIGNATURES = {
     "scgib_eval_append": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I64, _P, _P]),
     "scgib_eval_keys": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "scgib_eval_scan": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "scgib_collate_max_batch": (_I64, []),
+    "scgib_collate_ws_words": (_I64, [_I64]),
+    "scgib_collate_plan": (ctypes.c_int, [_P, _I32, _I32, _I32, _P]),
+    "scgib_collate_fill": (ctypes.c_int, [_P, _I32, _P]),
 }
 
 
@@ -233,6 +237,17 @@ class RunningUpdate(ctypes.Structure):
                 ("n_graphs", ctypes.c_int64), ("momentum", ctypes.c_float),
                 ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p),
                 ("num_batches_tracked", ctypes.c_void_p)]
+
+
+class CollateDesc(ctypes.Structure):
+    """scgib_collate_desc (include/scgib.h)."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in
+                 ("node_off", "edge_off", "rp_local", "col", "x", "y", "ego_nodes", "ego_edges",
+                  "perm", "srcs", "cursor", "state", "ws", "slot_ids", "labels", "ids")] +
+                [(n, ctypes.c_int64) for n in
+                 ("M", "S", "n_cap", "e_cap", "ego_n_cap", "ego_e_cap", "o_rowptr", "o_col",
+                  "o_gptr", "o_dims", "o_x", "blob_bytes")] +
+                [(n, ctypes.c_int32) for n in ("B", "F", "T", "pad_")])
 
 
 ABI_VERSION = 24

@@ -904,3 +904,410 @@ def logm_targets(g: GraphBatch, k: int, ego=None) -> LogMSparse:
                                   "walk count outside the exact domain)")
     return LogMSparse(s_in, s_sym, C, k, ego.graph_ptr, ego_nodes, g.graph_ptr, err,
                       max(g.max_graph_nodes, 1), g.dims)
+
+
+# ---------------------------------------------------------------------------
+# device-side collation of shuffled batches from a resident dataset
+# (csrc/collate.hip)
+# ---------------------------------------------------------------------------
+COLLATE_MAX_BATCH = 4096  # scgib_collate_max_batch(): the plan launch is one workgroup
+EGO_MAX_GRAPH_NODES = 512  # the ego builder's bitmap width
+_DS_CHUNK = 2048  # molecules per host pass (ingest, k >= 2 ego bounds)
+
+
+def _segment_sum(values, ptr):
+    """Sums of ``values`` over the non-empty segments ptr[i]:ptr[i+1]."""
+    if len(ptr) <= 1:
+        return np.zeros(0, np.int64)
+    return np.add.reduceat(np.asarray(values, np.int64), ptr[:-1])
+
+
+def _molecule_ego_bounds(gptr, rowptr, deg, col, selfloops, k):
+    """ego_bounds per molecule: (ego nodes [M], ego edge bound [M]) of flat
+    molecule CSRs (molecule-local ``col``).  k = 1 in closed form; k >= 2 by
+    the host reachability over chunks of molecules (block-diagonal, so one
+    sparse product per chunk) with per-molecule segment sums."""
+    deg64 = deg.astype(np.int64)
+    if k == 1:
+        ball = 1 + deg64 - selfloops
+        return _segment_sum(ball, gptr), _segment_sum(deg64 * ball, gptr)
+    import scipy.sparse as sp
+    M = len(gptr) - 1
+    nodes, edges = np.zeros(M, np.int64), np.zeros(M, np.int64)
+    for a in range(0, M, _DS_CHUNK):
+        b = min(a + _DS_CHUNK, M)
+        n0, n1 = int(gptr[a]), int(gptr[b])
+        e0, e1 = int(rowptr[n0]), int(rowptr[n1])
+        n = n1 - n0
+        local_ptr = gptr[a:b + 1] - n0
+        owner_off = np.repeat(local_ptr[:-1], np.diff(local_ptr))  # node offset of each node's molecule
+        indptr = rowptr[n0:n1 + 1] - e0
+        cols = col[e0:e1].astype(np.int64) + np.repeat(owner_off, deg64[n0:n1])
+        adj = sp.csr_matrix((np.ones(len(cols), np.int8), cols, indptr), shape=(n, n))
+        step = (adj + sp.identity(n, dtype=np.int8, format="csr")).astype(bool).astype(np.int32)
+        r = step
+        for _ in range(k - 1):
+            r = (r @ step).astype(bool).astype(np.int32)
+        r.sort_indices()
+        nodes[a:b] = _segment_sum(np.diff(r.indptr), local_ptr)
+        edges[a:b] = _segment_sum(r @ deg64[n0:n1], local_ptr)
+    return nodes, edges
+
+
+class DeviceDataset:
+    """A molecule dataset resident on the device as flat per-molecule CSRs,
+    for device-side collation (DeviceLoader).  A collated batch is the offset
+    concatenation of its molecules' rows, so the stored rows are exactly what
+    ``collate_pyg`` / ``CSRCache.collate`` produce (the same ingest, once, on
+    the host).  Features are stored as given (the caller normalises them).
+
+    Device arrays (``arrays``; the same names on the host in ``host``):
+    ``node_off`` / ``edge_off`` [M+1] int64, ``rp_local`` [nodes] int32 (row
+    pointer of a node inside its molecule's edge range), ``col`` [edges] int32
+    (molecule-local), ``x`` [nodes, F] fp32, ``y`` [M, T] fp32 or None (NaN
+    kept), ``ego_nodes`` / ``ego_edges`` [M] int32 (``ego_bounds`` of each
+    molecule for ``k``).  Host facts: ``node_counts`` / ``edge_counts`` [M],
+    ``max_graph_nodes``, ``max_in_degree``, ``dropped`` (one-atom molecules
+    left out under ``drop_single_atom``)."""
+
+    def __init__(self, gptr, deg, col, x, y, device, k, drop_single_atom=False):
+        gptr = np.asarray(gptr, np.int64)
+        deg = np.asarray(deg, np.int32)
+        col = np.asarray(col, np.int32)
+        x = np.ascontiguousarray(np.asarray(x, np.float32))
+        if x.ndim != 2 or x.shape[0] != gptr[-1] or len(deg) != gptr[-1] or \
+                int(deg.astype(np.int64).sum()) != len(col):
+            raise GraphIngestError("DeviceDataset: inconsistent flat arrays")
+        if y is not None:
+            y = np.asarray(y, np.float32)
+            y = None if y.size == 0 else np.ascontiguousarray(y.reshape(len(gptr) - 1, -1))
+        counts = np.diff(gptr)
+        self.dropped = 0
+        small = counts < 2
+        if small.any():
+            if not drop_single_atom:
+                raise GraphIngestError(
+                    f"DeviceDataset: molecule {int(np.flatnonzero(small)[0])} has fewer than two "
+                    "atoms (StaticBatch.pad refuses those; drop_single_atom=True leaves them out, "
+                    "as the reference skips them)")
+            keep = ~small
+            node_keep = np.repeat(keep, counts)
+            edge_keep = np.repeat(node_keep, deg)
+            deg, col, x = deg[node_keep], col[edge_keep], x[node_keep]
+            y = None if y is None else y[keep]
+            counts = counts[keep]
+            gptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            self.dropped = int(small.sum())
+        M = len(counts)
+        if M == 0:
+            raise GraphIngestError("DeviceDataset: no molecules")
+        if int(counts.max()) > EGO_MAX_GRAPH_NODES:
+            raise GraphIngestError(
+                f"DeviceDataset: molecule {int(counts.argmax())} has {int(counts.max())} atoms, "
+                f"above the ego builder's limit of {EGO_MAX_GRAPH_NODES}")
+        rowptr = np.concatenate([[0], np.cumsum(deg, dtype=np.int64)])
+        n_tot = int(gptr[-1])
+        owner = np.repeat(np.arange(M), counts)
+        node_count_of_edge = np.repeat(counts[owner], deg)
+        if len(col) and (col.min() < 0 or (col >= node_count_of_edge).any()):
+            raise GraphIngestError("DeviceDataset: an edge leaves its molecule")
+        edge_off = rowptr[gptr]
+        rp_local = (rowptr[:-1] - edge_off[owner]).astype(np.int32)
+        local_row = np.arange(n_tot) - gptr[owner]
+        rows = np.repeat(np.arange(n_tot), deg)
+        selfloops = np.bincount(rows[col == local_row[rows]], minlength=n_tot).astype(np.int64)
+        ego_n, ego_e = _molecule_ego_bounds(gptr, rowptr, deg, col, selfloops, int(k))
+        if len(ego_e) and max(int(ego_n.max()), int(ego_e.max())) >= 2 ** 31:
+            raise GraphIngestError("DeviceDataset: a molecule's ego bound passes int32")
+        self.k = int(k)
+        self.num_graphs, self.num_features = M, int(x.shape[1])
+        self.num_tasks = 0 if y is None else int(y.shape[1])
+        self.node_counts, self.edge_counts = counts, np.diff(edge_off)
+        self.max_graph_nodes = int(counts.max())
+        self.max_in_degree = int(deg.max()) if len(deg) else 0
+        self.host = {"node_off": gptr, "edge_off": edge_off.astype(np.int64), "rp_local": rp_local,
+                     "col": col, "x": x, "y": y, "ego_nodes": ego_n.astype(np.int32),
+                     "ego_edges": ego_e.astype(np.int32)}
+        self.device = torch.device(device)
+        # (a memory-mapped cache array is read-only: torch wants a writable source)
+        self.arrays = {key: None if v is None else
+                       torch.from_numpy(v if v.flags.writeable else v.copy()).to(self.device)
+                       for key, v in self.host.items()}
+
+    def __len__(self):
+        return self.num_graphs
+
+    @classmethod
+    def from_cache(cls, cache, device, k, drop_single_atom=False):
+        """From a cache.CSRCache (its flat arrays are already in ingest order)."""
+        return cls(np.asarray(cache.graph_ptr), np.asarray(cache.deg), np.asarray(cache.col),
+                   np.asarray(cache.x), np.asarray(cache.y), device, k, drop_single_atom)
+
+    @classmethod
+    def from_molecules(cls, molecules, device, k, labels=None, drop_single_atom=False):
+        """From PyG-style ``(edge_index, x)`` molecules, normalised through
+        collate_pyg (to_bidirected, (src, dst)-sorted) in chunks; a molecule
+        whose feature rows do not match its inferred node count raises."""
+        molecules = list(molecules)
+        counts, degs, cols, xs = [], [], [], []
+        for a in range(0, len(molecules), _DS_CHUNK):
+            g, _ = collate_pyg(molecules[a:a + _DS_CHUNK], skip_invalid=False)
+            if not g.host_info["validated"]:
+                raise GraphIngestError("DeviceDataset: an edge leaves its molecule")
+            rp = g.rowptr.numpy().astype(np.int64)
+            c = g.col.numpy().astype(np.int64)[: rp[-1]]
+            bnn = g.batch_num_nodes_host().astype(np.int64)
+            gp = np.concatenate([[0], np.cumsum(bnn)])
+            node_off = np.repeat(gp[:-1], bnn)
+            degs.append(np.diff(rp).astype(np.int32))
+            cols.append((c - np.repeat(node_off, np.diff(rp))).astype(np.int32))
+            xs.append(g.ndata["x"].numpy().astype(np.float32))
+            counts.append(bnn)
+        if not counts:
+            raise GraphIngestError("DeviceDataset: no molecules")
+        counts = np.concatenate(counts)
+        y = None
+        if labels is not None:
+            y = np.asarray(labels, np.float32).reshape(len(molecules), -1)
+        return cls(np.concatenate([[0], np.cumsum(counts)]), np.concatenate(degs),
+                   np.concatenate(cols), np.concatenate(xs), y, device, k, drop_single_atom)
+
+    def capacities(self, B, mode="worst", slack=1.0, samples=64, seed=0):
+        """The tuple StaticBatch.capacities returns, for batches of ``B``
+        molecules of this dataset.  ``"worst"``: the sums of the B largest
+        per-molecule node, edge and ego values, so no batch can overflow.
+        ``"sampled"``: the maxima over ``samples`` seeded random batches times
+        ``slack``, as StaticBatch.capacities takes them over host batches; a
+        batch above them is skipped by the loader (DeviceLoader.error)."""
+        B = int(B)
+        if not 1 <= B <= self.num_graphs:
+            raise _lib.ScgibError(f"capacities: batch size {B} outside 1..{self.num_graphs}")
+        per = [self.node_counts, self.edge_counts, self.host["ego_nodes"].astype(np.int64),
+               self.host["ego_edges"].astype(np.int64)]
+        if mode == "worst":
+            tops = [int(np.sort(v)[-B:].sum()) for v in per]
+        elif mode == "sampled":
+            rng = np.random.default_rng(seed)
+            tops = [0, 0, 0, 0]
+            for _ in range(int(samples)):
+                ids = rng.choice(self.num_graphs, B, replace=False)
+                tops = [max(t, int(v[ids].sum())) for t, v in zip(tops, per)]
+        else:
+            raise ValueError(f"capacities: mode {mode!r} (\"worst\" or \"sampled\")")
+        f = lambda v: int(v * slack) + 1  # noqa: E731
+        dmax = self.max_in_degree if self.k == 1 else 1 << 30
+        return f(tops[0]), f(tops[1]), self.max_graph_nodes, (f(tops[2]), f(tops[3]), dmax)
+
+
+def collate_blob_host(host, ids, static):
+    """The batch of molecules ``ids`` (in that order, repeats allowed) of a
+    DeviceDataset's host arrays (``dataset.host``) as ``static``'s blob, in
+    numpy: (blob uint8, labels [B, T] or None, ids int32).  What
+    scgib_collate_fill writes into a ring slot, and byte for byte what
+    ``static.pad(collate_pyg([...]))["blob"]`` holds:
+
+      rowptr [n_cap+1]  edge offset of the molecule + the node's local row
+                        pointer; rowptr[n..] = e
+      col [max(e_cap,1)] molecule-local id + node offset of the molecule; 0 past e
+      graph_ptr [B+1]   node offsets
+      dims [4]          n, e, the ego error word (0), 0
+      x [n_cap, F]      the molecules' feature rows; 0 past n
+    each section at its 256-byte aligned offset (StaticBatch._layout)."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    node_off, edge_off = host["node_off"], host["edge_off"]
+    if len(ids) != static.B or (len(ids) and (ids.min() < 0 or ids.max() >= len(node_off) - 1)):
+        raise _lib.ScgibError("collate_blob_host: ids do not form one batch of the dataset")
+    n_i = node_off[ids + 1] - node_off[ids]
+    e_i = edge_off[ids + 1] - edge_off[ids]
+    gptr = np.concatenate([[0], np.cumsum(n_i)])
+    eoff = np.concatenate([[0], np.cumsum(e_i)])
+    n, e = int(gptr[-1]), int(eoff[-1])
+    ns, es = static.graph.ego_caps[:2]
+    if n > static.n_cap or e > static.e_cap or int(host["ego_nodes"][ids].sum()) > ns or \
+            int(host["ego_edges"][ids].sum()) > es:
+        raise _lib.ScgibError("collate_blob_host: the batch does not fit the capacities")
+    nodes = np.repeat(node_off[ids] - gptr[:-1], n_i) + np.arange(n)
+    edges = np.repeat(edge_off[ids] - eoff[:-1], e_i) + np.arange(e)
+    o = static._layout()
+    blob = np.zeros(o[-1], np.uint8)
+    rp = np.full(static.n_cap + 1, e, np.int32)
+    rp[:n] = host["rp_local"][nodes] + np.repeat(eoff[:-1], n_i)
+    blob[o[0]:o[0] + rp.nbytes] = rp.view(np.uint8)
+    col = (host["col"][edges].astype(np.int64) + np.repeat(gptr[:-1], e_i)).astype(np.int32)
+    blob[o[1]:o[1] + col.nbytes] = col.view(np.uint8)
+    gp = gptr.astype(np.int32)
+    blob[o[2]:o[2] + gp.nbytes] = gp.view(np.uint8)
+    blob[o[3]:o[3] + 8] = np.array([n, e], np.int32).view(np.uint8)
+    x = np.ascontiguousarray(host["x"][nodes])
+    blob[o[4]:o[4] + x.nbytes] = x.view(np.uint8).reshape(-1)
+    labels = None if host["y"] is None else host["y"][ids]
+    return blob, labels, ids.astype(np.int32)
+
+
+class DeviceLoader:
+    """Shuffled batches of a DeviceDataset collated on the device, one step
+    ahead of a replayed step over ``static`` (csrc/collate.hip).
+
+    ``pool`` is a ring of three blobs in ``static``'s layout (one allocation),
+    shaped like ``StaticBatch.pool(...)``: ``static.load_next(loader.pool, pf)``
+    and ``EgoPrefetch(static, loader.pool)`` consume it unchanged.  In step t,
+    load_next reads slot t % 3, the ego prefetch reads slot (t + 1) % 3 and
+    ``collate_ahead()`` — enqueued after load_next — builds batch t + 2 into
+    slot (t + 2) % 3, the slot neither of them touches.
+
+    Batch sequence: S = M // B steps per epoch (S >= 3); global batch j holds
+    molecules ``epoch_permutation(j // S)[(j % S) * B : + B]``.  The M % B
+    molecules at the end of each permutation are dropped that epoch (the
+    reference trains on the partial batch; a captured graph has a fixed B).
+    The permutations of even and odd epochs sit in two device buffers;
+    ``begin_epoch(e)`` uploads epoch e + 1's.  If it is never called the two
+    buffers repeat.
+
+    ``labels`` [B, T] / ``ids`` [B]: the labels and molecule ids of the batch
+    the step is training on, valid for work enqueued after ``collate_ahead()``
+    (``ride(prefetch)`` moves that call onto the ego prefetch's queue, off the
+    step's critical path, for steps that do not read the labels).
+    A batch above the capacities of ``static`` is not written (its slot keeps
+    the earlier batch, labels and ids follow the slot) and counted:
+    ``error()``."""
+
+    def __init__(self, dataset, static, seed=0, shuffle=True):
+        ds = dataset
+        B, M = int(static.B), ds.num_graphs
+        if not 1 <= B <= COLLATE_MAX_BATCH:
+            raise _lib.ScgibError(f"DeviceLoader: batch size {B} outside 1..{COLLATE_MAX_BATCH}")
+        S = M // B
+        if S < 3:
+            raise _lib.ScgibError(f"DeviceLoader: {M} molecules give {S} batches of {B} per epoch; "
+                                  "the three-slot ring needs at least 3")
+        caps = static.graph.ego_caps or ()
+        if len(caps) < 2:
+            raise _lib.ScgibError("DeviceLoader: the static batch has no ego capacities")
+        if static.n_feat != ds.num_features or static.k != ds.k:
+            raise _lib.ScgibError("DeviceLoader: static batch and dataset differ in feature "
+                                  "width or ego radius k")
+        if ds.max_graph_nodes > static.graph.max_graph_nodes:
+            raise _lib.ScgibError("DeviceLoader: the dataset has a larger molecule than the "
+                                  "static batch's bitmap width")
+        if len(caps) > 2 and ds.max_in_degree > caps[2]:
+            raise _lib.ScgibError("DeviceLoader: the dataset's max in-degree exceeds the "
+                                  "static batch's ego builder bound")
+        dev = static.blob.device
+        if ds.device != dev:
+            raise _lib.ScgibError("DeviceLoader: dataset and static batch on different devices")
+        self.dataset, self.static = ds, static
+        self.seed, self.shuffle = int(seed), bool(shuffle)
+        self.B, self.M, self.steps_per_epoch = B, M, S
+        nbytes = static.blob.numel()
+        self.ring = torch.zeros(3 * nbytes, dtype=torch.uint8, device=dev)
+        self.slots = [self.ring[i * nbytes:(i + 1) * nbytes] for i in range(3)]
+        i32 = torch.int32
+        self.pool = {"table": torch.tensor([s.data_ptr() for s in self.slots], dtype=torch.int64,
+                                           device=dev),
+                     "cursor": torch.zeros(2, dtype=i32, device=dev), "n": 3,
+                     "batches": [{"blob": s} for s in self.slots]}
+        T = ds.num_tasks
+        self.labels = torch.zeros(B, T, dtype=torch.float32, device=dev)
+        self.ids = torch.zeros(B, dtype=i32, device=dev)
+        self.state = torch.zeros(4, dtype=i32, device=dev)  # position in [0, 2S), overflow count
+        self.perm = torch.zeros(2 * M, dtype=i32, device=dev)
+        # scgib_collate_ws_words(B): header, graph_ptr, edge offsets, the molecules' 64-bit bases
+        self._ws = torch.zeros((8 + 2 * (B + 1) + 1) // 2 * 2 + 4 * B, dtype=i32, device=dev)
+        self._slot_ids = torch.zeros(3 * B, dtype=i32, device=dev)
+        self._pinned = [None, None]  # begin_epoch's host staging and its copy's event
+        a = ds.arrays
+        o = static._layout()
+        p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+        self._desc = _lib.CollateDesc(
+            node_off=p(a["node_off"]), edge_off=p(a["edge_off"]), rp_local=p(a["rp_local"]),
+            col=p(a["col"]), x=p(a["x"]), y=p(a["y"]), ego_nodes=p(a["ego_nodes"]),
+            ego_edges=p(a["ego_edges"]), perm=p(self.perm), srcs=p(self.pool["table"]),
+            cursor=p(self.pool["cursor"]), state=p(self.state), ws=p(self._ws),
+            slot_ids=p(self._slot_ids), labels=p(self.labels), ids=p(self.ids), M=M, S=S,
+            n_cap=static.n_cap, e_cap=static.e_cap, ego_n_cap=int(caps[0]), ego_e_cap=int(caps[1]),
+            o_rowptr=o[0], o_col=o[1], o_gptr=o[2], o_dims=o[3], o_x=o[4], blob_bytes=nbytes,
+            B=B, F=ds.num_features, T=T, pad_=0)
+
+    # ----- the batch sequence (host side) ---------------------------------
+    def epoch_permutation(self, e):
+        """perm_e on the host (int64 numpy): drawn from a CPU generator seeded
+        by (seed, e); the identity without shuffling."""
+        if not self.shuffle:
+            return np.arange(self.M, dtype=np.int64)
+        return np.random.default_rng([self.seed, int(e)]).permutation(self.M).astype(np.int64)
+
+    def batch_ids(self, j):
+        """Molecule ids of global batch j (begin_epoch called every epoch)."""
+        S, B = self.steps_per_epoch, self.B
+        return self.epoch_permutation(j // S)[(j % S) * B:(j % S) * B + B]
+
+    def _perm_slice(self, e):
+        return self.perm[(e % 2) * self.M:(e % 2 + 1) * self.M]
+
+    # ----- device side -------------------------------------------------------
+    def _launch(self, ahead, slot, advance, labels):
+        d = ctypes.byref(self._desc)
+        _lib.call("scgib_collate_plan", d, ahead, slot, advance, _stream())
+        _lib.call("scgib_collate_fill", d, labels, _stream())
+
+    def prime(self):
+        """Eager, before the capture: perm_0 and perm_1, batches 0 and 1 into
+        slots 0 and 1 (slot 2 holds batch 0 until step 0 builds batch 2 over
+        it), cursors reset."""
+        if self.ring.device.type != "cuda":
+            raise _lib.ScgibError("DeviceLoader.prime needs a HIP device (no CPU fallback)")
+        for e in (0, 1):
+            self._perm_slice(e).copy_(torch.from_numpy(self.epoch_permutation(e).astype(np.int32)))
+        self.pool["cursor"].zero_()
+        self.state.zero_()
+        for ahead, slot in ((0, 2), (0, 0), (1, 1)):
+            self._launch(ahead, slot, 0, 0)
+        if self.error():
+            raise _lib.ScgibError("DeviceLoader.prime: the first batches do not fit the "
+                                  "capacities of the static batch")
+
+    def collate_ahead(self):
+        """Once per step after load_next, on a stream ordered after it
+        (capturable; no host synchronisation): batch t + 2 into slot
+        (t + 2) % 3, batch t's labels and ids into ``labels`` / ``ids``, and the
+        position moves on."""
+        self._launch(2, -1, 1, 1)
+
+    def ride(self, prefetch):
+        """Move collate_ahead onto the ego prefetch's queue: from now on every
+        ``prefetch.prefetch()`` — the encoder pair's side tail, in the ego
+        chain's idle stretch through the loss section — is followed by
+        collate_ahead() on the same stream, which the backward joins back
+        before the next load_next.  The step then makes no collate_ahead call
+        of its own, and ``labels`` / ``ids`` are valid only after that join
+        (a loss that reads the labels wants collate_ahead() on the main queue
+        instead).  Call it after ``prefetch.prime()``."""
+        if prefetch.pool is not self.pool:
+            raise _lib.ScgibError("DeviceLoader.ride: the EgoPrefetch was made for another pool")
+        build = prefetch.prefetch
+
+        def prefetch_then_collate():
+            build()
+            self.collate_ahead()
+
+        prefetch.prefetch = prefetch_then_collate
+
+    def begin_epoch(self, e):
+        """On the step's stream before the first step of epoch e >= 1 is
+        enqueued: perm_{e+1} into buffer (e + 1) % 2, whose last reader (the
+        collation of epoch e - 1's last batch) ran two steps earlier."""
+        e = int(e)
+        buf = (e + 1) % 2
+        host = torch.from_numpy(self.epoch_permutation(e + 1).astype(np.int32))
+        if self._pinned[buf] is not None:
+            self._pinned[buf][1].synchronize()  # the staging's earlier copy has left it
+            self._pinned[buf][0].copy_(host)
+        else:
+            self._pinned[buf] = [host.pin_memory(), torch.cuda.Event()]
+        self._perm_slice(e + 1).copy_(self._pinned[buf][0], non_blocking=True)
+        self._pinned[buf][1].record()
+
+    def error(self):
+        """How many batches did not fit the capacities and were skipped
+        (sticky) — a device read, for checks outside the loop."""
+        return int(self.state[1].item())
