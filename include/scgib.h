@@ -302,6 +302,28 @@ int scgib_gt_qkv_bwd(const float *dq, const float *dk, const float *dv, const fl
                      int64_t n_nodes, float *dh, float *slab, const int32_t *dims,
                      scgib_stream_t stream);
 
+/* ---- the Transformer encoder's folded entry (csrc/gt_embed.hip) -------------
+ *   h0 = (x[map] Wt^T) We^T   [n][64]
+ * x [rows_x][n_feat]: the raw normalised features, 1 <= n_feat <= 16; wt =
+ * transfer_d.weight [32][n_feat], we = embedding_h.weight [64][32] (neither
+ * has a bias); map (int32 [n], may be NULL: the identity, rows_x >= n then)
+ * gives the row of x behind each row of h0 (an ego batch's parent rows); an
+ * entry outside [0, rows_x) reads the nearest row of x.  The [n][32]
+ * intermediate is never written: the backward recomputes it.
+ * scgib_gt_embed_bwd: slab = scgib_gt_embed_slabs(n) rows of
+ * scgib_gt_embed_slab_width(n_feat) floats, dWe [64][32] | dWt [32][n_feat];
+ * the caller sums the rows with scgib_slab_reduce_multi (fixed order).  No
+ * gradient for x.  n_feat outside 1..16: SCGIB_EUNSUPPORTED (slab_width: 0).
+ * Capacity mode: rows >= dims[0] of h0 are zeros and add nothing to the slabs. */
+int64_t scgib_gt_embed_slabs(int64_t n_nodes);
+int64_t scgib_gt_embed_slab_width(int32_t n_feat);
+int scgib_gt_embed_fwd(const float *x, int32_t n_feat, int64_t rows_x, const int32_t *map,
+                       const float *wt, const float *we, int64_t n_nodes, float *h0,
+                       const int32_t *dims, scgib_stream_t stream);
+int scgib_gt_embed_bwd(const float *dh0, const float *x, int32_t n_feat, int64_t rows_x,
+                       const int32_t *map, const float *wt, const float *we, int64_t n_nodes,
+                       float *slab, const int32_t *dims, scgib_stream_t stream);
+
 /* ---- A5 fused: one GIN layer = GINConv(MLP) + BatchNorm1d + ReLU -----------
  * Replaces, per layer, DGL GINConv + nn.Linear x2 + ReLU + nn.BatchNorm1d +
  * F.relu of GIN.forward (models.py:63-71) and their autograd backward.

@@ -70,6 +70,10 @@ SIGNATURES = {
                                         _P, _P, _P, _P]),
     "scgib_gt_out_bwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "scgib_gt_qkv_bwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    "scgib_gt_embed_slabs": (_I64, [_I64]),
+    "scgib_gt_embed_slab_width": (_I64, [_I32]),
+    "scgib_gt_embed_fwd": (ctypes.c_int, [_P, _I32, _I64, _P, _P, _P, _I64, _P, _P, _P]),
+    "scgib_gt_embed_bwd": (ctypes.c_int, [_P, _P, _I32, _I64, _P, _P, _P, _I64, _P, _P, _P]),
     "scgib_segment_sum": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     "scgib_segment_broadcast": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I64, _P, _P]),
     "scgib_egonet_workspace_bytes": (_I64, [_I64]),

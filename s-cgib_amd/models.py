@@ -34,15 +34,18 @@ Differences from the reference, all deliberate:
     deferred-reduce machinery), "GCN" and "GraphSAGE" (each layer one fused
     HIP launch forward and two backward, run through the plain two-stream
     encoder branch; DGL 1.1.0's GraphConv / SAGEConv semantics restated, not
-    linked) in Mainmodel and Mainmodel_continue; the fine-tune /
-    domain-adaptation heads take "GIN" only.  Transformer /
-    GraphTransformerLayer / MultiHeadAttentionLayer (models.py:807-918, on the
-    kernels of gt_layer.hip) are available as modules with the reference's
-    constructor arguments and state_dict keys, but not yet selectable by
-    ``encoder=``: "Transformer" as a string still raises.
+    linked) and "Transformer" (Transformer / GraphTransformerLayer /
+    MultiHeadAttentionLayer, models.py:807-918, on the kernels of
+    gt_layer.hip; in the step each encoder is one autograd node behind the
+    folded entry of gt_embed.hip, GT_FOLD) in all four model classes, with
+    the reference's constructor arguments and state_dict keys.  The strings
+    beyond those accepted before — "Transformer" anywhere, anything but "GIN"
+    in the fine-tune / domain-adaptation classes — are accepted with
+    ``models.ALL_ENCODER_STRINGS = True`` (off by default: see there).
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -329,18 +332,45 @@ class Transformer(nn.Module):
         return self.extract_features(g, h, drop_masks)
 
 
-ENCODERS = ("GIN", "GCN", "GraphSAGE")
+ENCODERS = ("GIN", "GCN", "GraphSAGE")  # by string without ALL_ENCODER_STRINGS
+ALL_ENCODERS = ENCODERS + ("Transformer",)  # the reference's ``--encoder`` values
+# Every model class takes every reference encoder string.  Off (the default):
+# the strings accepted are those from before the switch existed — ENCODERS in
+# Mainmodel / Mainmodel_continue, "GIN" alone in Mainmodel_finetuning /
+# Mainmodel_domainadapt — and anything else raises NotImplementedError, as it
+# did.  A checkpoint that records an encoder is rebuilt with it either way.
+ALL_ENCODER_STRINGS = False
+_LOADING = [0]  # > 0 while load_checkpoint builds a file's own levels
 
 
-def _make_encoder(encoder, in_dim, hidden_dim, args):
-    """One encoder of Mainmodel / Mainmodel_continue (models.py:573-587)."""
+@contextlib.contextmanager
+def _loading():
+    _LOADING[0] += 1
+    try:
+        yield
+    finally:
+        _LOADING[0] -= 1
+
+
+def _make_encoder(encoder, in_dim, hidden_dim, args, num_layers, num_heads, head=False):
+    """One encoder of a model class (models.py:156-167, :405-416, :573-587,
+    :1060-1071).  ``head``: a fine-tune / domain-adaptation class, whose own
+    encoders exist for state_dict parity only."""
+    if encoder not in ALL_ENCODERS:
+        raise NotImplementedError(f"encoder {encoder!r}: implemented are "
+                                  f"{', '.join(ALL_ENCODERS)}")
+    if not (ALL_ENCODER_STRINGS or _LOADING[0]) and \
+            encoder not in (("GIN",) if head else ENCODERS):
+        raise NotImplementedError(
+            f"encoder {encoder!r}: accepted here with models.ALL_ENCODER_STRINGS = True "
+            f"(off by default; without it: {'GIN' if head else ', '.join(ENCODERS)})")
     if encoder == "GIN":
         return GIN(in_dim, hidden_dim, _gin_layers(args))
     if encoder == "GCN":
         return GCN(in_dim, hidden_dim)
     if encoder == "GraphSAGE":
         return GraphSAGE(in_dim, hidden_dim)
-    raise NotImplementedError(f"encoder {encoder!r}: implemented are {', '.join(ENCODERS)}")
+    return Transformer(in_dim, hidden_dim, num_layers, num_heads, getattr(args, "device", None))
 
 
 class Set2Set(nn.Module):
@@ -396,6 +426,10 @@ DEVICE_NOISE = True
 # heads (C > 16), the MAE / RMSE / BCE-with-logits losses and MetricWrapper's
 # NaN-masked "ignore-flatten" losses on csrc/task_head.hip
 FUSE_HEAD = True
+# two Transformer encoders of width 64 behind the folded entry, each one
+# autograd node with one weight-gradient reduce and a dropout lane of its own
+# (ops.gt_encoder_x); off: the generic two-stream branch
+GT_FOLD = True
 
 
 _GRAPH_ATTRS = ("graph_features", "subgraphs_features", "_last_z1", "_last_kl_mean")
@@ -558,6 +592,28 @@ class _SCGIBCore(nn.Module):
             subgraphs_features, sub_readout, graph_features = outs[0], outs[1], outs[2]
             t = outs[3] if len(outs) > 3 else None
             return ego, (graph_features, subgraphs_features, sub_readout, t, drawn.get("u"))
+        e1, e2 = enc_owner.Encoder1, enc_owner.Encoder2
+        if (GT_FOLD and isinstance(e1, Transformer) and isinstance(e2, Transformer)
+                and all(e.hidden_dim == 64 and e.embedding_h.in_features == 32
+                        and e.layers[0].num_heads in ops.GT_HEADS for e in (e1, e2))
+                and td.bias is None and td.out_features == 32
+                and batch_x.shape[1] <= 16 and not batch_x.requires_grad):
+            # each Transformer one autograd node behind the folded entry
+            # (ops.gt_encoder_x): the features gathered in-kernel, transfer_d
+            # and embedding_h one launch, one weight-gradient reduce per
+            # encoder; the ego chain draws its dropout from lane 1, so either
+            # state is advanced by one chain in stream order (reproducible
+            # whether or not the chains overlap)
+            with torch.cuda.stream(side):
+                ego = G.egonet_batch(batch_g, self.k_transition)
+                subgraphs_features, sub_readout = ops.gt_encoder_x(
+                    batch_x, ego, e2, td, ego.ndata["_ID"],
+                    readout=(ego.graph_ptr, ego.batch_size, ego.seg_dims), lane=1)
+            graph_features = ops.gt_encoder_x(batch_x, batch_g, e1, td, lane=0)
+            main.wait_stream(side)
+            subgraphs_features.record_stream(main)
+            sub_readout.record_stream(main)
+            return ego, (graph_features, subgraphs_features, sub_readout, None, None)
         with torch.cuda.stream(side):
             if fold:
                 ego = G.egonet_batch(batch_g, self.k_transition)
@@ -653,9 +709,9 @@ class Mainmodel(_SCGIBCore):
         self.reconstructX = nn.Sequential(nn.Linear(self.hidden_dim, self.in_dim))
         self.MLP = nn.Sequential(nn.Linear(2 * hidden_dim, hidden_dim), nn.ReLU(),
                                  nn.Linear(hidden_dim, hidden_dim))
-        self.encoder_name = encoder
-        self.Encoder1 = _make_encoder(encoder, self.in_dim, hidden_dim, args)
-        self.Encoder2 = _make_encoder(encoder, self.in_dim, hidden_dim, args)
+        self.encoder_name, self.num_layers, self.num_heads = encoder, num_layers, num_heads
+        self.Encoder1 = _make_encoder(encoder, self.in_dim, hidden_dim, args, num_layers, num_heads)
+        self.Encoder2 = _make_encoder(encoder, self.in_dim, hidden_dim, args, num_layers, num_heads)
         self.compressor = nn.Sequential(nn.Linear(hidden_dim, hidden_dim),
                                         nn.BatchNorm1d(hidden_dim), nn.ReLU(),
                                         nn.Linear(hidden_dim, 1))
@@ -728,9 +784,9 @@ class Mainmodel_continue(_SCGIBCore):
                                      nn.Linear(hidden_dim, out_dim))
         self.MLP = nn.Sequential(nn.Linear(2 * hidden_dim, hidden_dim), nn.ReLU(),
                                  nn.Linear(hidden_dim, hidden_dim))
-        self.encoder_name = encoder
-        self.Encoder1 = _make_encoder(encoder, self.in_dim, hidden_dim, args)
-        self.Encoder2 = _make_encoder(encoder, self.in_dim, hidden_dim, args)
+        self.encoder_name, self.num_layers, self.num_heads = encoder, num_layers, num_heads
+        self.Encoder1 = _make_encoder(encoder, self.in_dim, hidden_dim, args, num_layers, num_heads)
+        self.Encoder2 = _make_encoder(encoder, self.in_dim, hidden_dim, args, num_layers, num_heads)
         self.model = load_checkpoint(cp_filename, args)
         for p in self.model.parameters():
             p.requires_grad = True
@@ -826,10 +882,11 @@ class Mainmodel_domainadapt(_SCGIBCore):
                                          nn.Linear(hidden_dim, out_dim))
         self.MLP = nn.Sequential(nn.Linear(2 * hidden_dim, hidden_dim), nn.ReLU(),
                                  nn.Linear(hidden_dim, hidden_dim))
-        if encoder != "GIN":
-            raise NotImplementedError(f"encoder {encoder!r}: only GIN is on the hot path")
-        self.Encoder1 = GIN(self.in_dim, hidden_dim, _gin_layers(args))
-        self.Encoder2 = GIN(self.in_dim, hidden_dim, _gin_layers(args))
+        self.encoder_name, self.num_layers, self.num_heads = encoder, num_layers, num_heads
+        self.Encoder1 = _make_encoder(encoder, self.in_dim, hidden_dim, args, num_layers, num_heads,
+                                      True)
+        self.Encoder2 = _make_encoder(encoder, self.in_dim, hidden_dim, args, num_layers, num_heads,
+                                      True)
         self.model = load_checkpoint(cp_filename, args)
         for p in self.model.parameters():
             p.requires_grad = True
@@ -936,10 +993,11 @@ class Mainmodel_finetuning(nn.Module):
                                      nn.Linear(hidden_dim, out_dim))
         self.MLP = nn.Sequential(nn.Linear(2 * hidden_dim, hidden_dim), nn.ReLU(),
                                  nn.Linear(hidden_dim, hidden_dim))
-        if encoder != "GIN":
-            raise NotImplementedError(f"encoder {encoder!r}: only GIN is on the hot path")
-        self.Encoder1 = GIN(self.in_dim, hidden_dim, _gin_layers(args))
-        self.Encoder2 = GIN(self.in_dim, hidden_dim, _gin_layers(args))
+        self.encoder_name, self.num_layers, self.num_heads = encoder, num_layers, num_heads
+        self.Encoder1 = _make_encoder(encoder, self.in_dim, hidden_dim, args, num_layers, num_heads,
+                                      True)
+        self.Encoder2 = _make_encoder(encoder, self.in_dim, hidden_dim, args, num_layers, num_heads,
+                                      True)
         self.model = load_checkpoint(cp_filename, args)
         freeze_like_reference(self.model)
         self.compressor = nn.Sequential(nn.Linear(hidden_dim, hidden_dim),
@@ -1060,13 +1118,19 @@ def save_checkpoint(model, path, args=None, in_dim=None, num_classes=1):
     cfg.update(kind=type(model).__name__, in_dim=in_dim, hidden_dim=model.hidden_dim,
                k_transition=model.k_transition, num_classes=num_classes)
     levels, encoders, m = [], [], model  # the wrapper chain (continue / DA around a Mainmodel)
+    depths, heads = [], []
     while m is not None:
         levels.append([type(m).__name__, int(m.transfer_d.weight.shape[1])])
         encoders.append(str(getattr(m, "encoder_name", "GIN")))
+        depths.append(int(getattr(m, "num_layers", 4)))
+        heads.append(int(getattr(m, "num_heads", 4)))
         m = getattr(m, "model", None)
     cfg["levels"] = levels
     # the encoder of each level (files without the entry: GIN at every level)
     cfg["encoder"], cfg["encoders"] = encoders[0], encoders
+    # ... and its constructor's num_layers / num_heads (a Transformer's depth
+    # and head count; files without the entries: 4 and 4)
+    cfg["num_layers"], cfg["num_heads"] = depths, heads
     torch.save({"config": cfg, "state_dict": model.state_dict()}, path)
 
 
@@ -1100,7 +1164,8 @@ def model_from_state(levels, cfg, sd, args=None):
         setattr(ns, k, cfg.get(k, getattr(args, k, None)))
     if ns.task is None:
         ns.task = "graph_classification"
-    m = _build_levels([(str(k), int(f)) for k, f in levels], ns, cfg)
+    with _loading():  # the file's own encoders, whatever ALL_ENCODER_STRINGS says
+        m = _build_levels([(str(k), int(f)) for k, f in levels], ns, cfg)
     m.load_state_dict(sd)
     return m
 
@@ -1108,9 +1173,12 @@ def model_from_state(levels, cfg, sd, args=None):
 def _build_levels(levels, ns, cfg, depth=0):
     """An untrained module for load_state_dict: levels = [(kind, F), ...] from
     the outermost wrapper down to the Mainmodel it wraps; each level's encoder
-    from cfg["encoders"] (cfg["encoder"] for all, "GIN" in files without)."""
+    from cfg["encoders"] (cfg["encoder"] for all, "GIN" in files without) and
+    its num_layers / num_heads from cfg's lists (4 and 4 in files without)."""
     (kind, f_in), rest = levels[0], levels[1:]
-    dims = (f_in, cfg["hidden_dim"], 4, 4, cfg["k_transition"])
+    nl, nh = cfg.get("num_layers") or [], cfg.get("num_heads") or []
+    dims = (f_in, cfg["hidden_dim"], int(nl[depth]) if depth < len(nl) else 4,
+            int(nh[depth]) if depth < len(nh) else 4, cfg["k_transition"])
     encs = cfg.get("encoders") or []
     enc = str(encs[depth]) if depth < len(encs) else str(cfg.get("encoder", "GIN"))
     if kind == "Mainmodel":

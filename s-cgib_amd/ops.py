@@ -2607,31 +2607,38 @@ def conv_encoder(h, graph, module):
 GT_HEADS = (1, 2, 4, 8, 16)
 GT_FFN = 2 * HIDDEN
 
-# Dropout of the FFN: {seed, offset} (int64) per device, a state of its own —
-# the compression noise state gives exactly one draw per step
+# Dropout of the FFN: {seed, offset} (int64) per device and lane, a state of
+# its own — the compression noise state gives exactly one draw per step
 # (NoisePrefetch).  The FFN kernel advances the offset itself, so every launch
-# and every graph replay draws a fresh mask.  One state per device: launches
-# that draw on two streams at once take their offsets in the order they run.
-_DROPOUT_STATES = {}  # device index -> int64 [seed, offset]
+# and every graph replay draws a fresh mask.  Launches that draw from ONE state
+# on two streams at once take their offsets in the order they run, and two in
+# flight together can read the same offset: a chain that runs beside another
+# one draws from a lane of its own (gt_encoder_x's ``lane``: the model step
+# gives Encoder1 lane 0 and Encoder2, the ego chain on the side stream, lane
+# 1), so each state is read and advanced by one chain, in stream order only.
+_DROPOUT_STATES = {}  # (device index, lane) -> int64 [seed, offset]
 
 
-def dropout_state(device):
-    """The device's dropout state; created on first use with a seed drawn from
-    torch's default CPU generator.  Create it outside graph capture."""
-    idx = torch.device(device).index or 0
-    st = _DROPOUT_STATES.get(idx)
+def dropout_state(device, lane=0):
+    """The device's dropout state of ``lane``; created on first use with a seed
+    drawn from torch's default CPU generator (each lane draws its own).  Create
+    it outside graph capture."""
+    key = (torch.device(device).index or 0, int(lane))
+    if key[1] < 0:
+        raise _lib.ScgibError(f"dropout_state: lane {lane}")
+    st = _DROPOUT_STATES.get(key)
     if st is None:
         if torch.cuda.is_current_stream_capturing():
             raise _lib.ScgibError("device dropout state must be created outside graph capture "
                                   "(run one eager step or call ops.seed_dropout first)")
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        st = _DROPOUT_STATES[idx] = torch.tensor([seed, 0], dtype=torch.int64, device=device)
+        st = _DROPOUT_STATES[key] = torch.tensor([seed, 0], dtype=torch.int64, device=device)
     return st
 
 
-def seed_dropout(device, seed, offset=0):
-    """Reset the device dropout stream (seed, offset) in place."""
-    st = dropout_state(device)
+def seed_dropout(device, seed, offset=0, lane=0):
+    """Reset the device dropout stream (seed, offset) of ``lane`` in place."""
+    st = dropout_state(device, lane)
     st.copy_(torch.tensor([int(seed), int(offset)], dtype=torch.int64))
     return st
 
@@ -2716,6 +2723,78 @@ def graph_attention(q, k, v, graph, num_heads, return_score=False):
 _GT_SLABS = 4  # FFN_layer2 + LN2 | FFN_layer1 | O + LN1 | Q, K, V
 
 
+def _gt_slab_layout():
+    """(widths, offsets) of a layer's four weight-gradient rows, concatenated."""
+    widths = [int(_lib.query("scgib_gt_slab_width", i)) for i in range(_GT_SLABS)]
+    return widths, [sum(widths[:i]) for i in range(_GT_SLABS + 1)]
+
+
+def _gt_layer_fwd(h, graph, heads, training, drop_mask, aux, P, st, lane=0):
+    """The five forward launches of one layer (P: its 16 used tensors, fp32):
+    (out, the tensors its backward reads)."""
+    n, dev = h.shape[0], h.device
+    wq, bq, wk, bk, wv, bv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2 = P
+    new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+    q, k, v = new(n, HIDDEN), new(n, HIDDEN), new(n, HIDDEN)
+    _lib.call("scgib_gt_qkv_fwd", _p(h), _p(wq), _p(bq), _p(wk), _p(bk), _p(wv), _p(bv), n,
+              _p(q), _p(k), _p(v), _p(graph.dims), st)
+    attn, z, score = _gt_attn_fwd(q, k, v, graph, heads, aux is not None)
+    pre1, stats1, h1 = new(n, HIDDEN), new(n, 2), new(n, HIDDEN)
+    _lib.call("scgib_gt_out_fwd", _p(attn), _p(h), _p(wo), _p(bo), _p(g1), _p(be1), n,
+              _p(pre1), _p(stats1), _p(h1), _p(graph.dims), st)
+    r, bits = new(n, GT_FFN), new(n, 4, dtype=torch.int32)
+    pos = new(n, 4, dtype=torch.int32) if aux is not None else None
+    keep = new(n, 4, dtype=torch.int32) if aux is not None else None
+    pre2, stats2, out = new(n, HIDDEN), new(n, 2), new(n, HIDDEN)
+    draw = training and drop_mask is None
+    rng = dropout_state(dev, lane) if draw else None
+    cnt = counters(dev, "gt_dropout", 1) if draw else None
+    _lib.call("scgib_gt_ffn_fwd", _p(h1), _p(w1), _p(b1), _p(w2), _p(b2), _p(g2), _p(be2), n,
+              int(training), _p(rng), _p(cnt), _p(drop_mask if training else None), _p(r),
+              _p(bits), _p(pos), _p(keep), _p(pre2), _p(stats2), _p(out), _p(graph.dims), st)
+    if aux is not None:
+        aux["ffn_pos"], aux["keep"], aux["score"] = _unpack_bits(pos), _unpack_bits(keep), score
+    return out, (h, q, k, v, attn, z, pre1, stats1, h1, r, bits, pre2, stats2,
+                 wq, wk, wv, wo, g1, w1, w2, g2)
+
+
+_GT_SAVED = 21  # tensors _gt_layer_fwd hands its backward
+
+
+def _gt_layer_bwd(g, saved, gr, heads, training, slabs, dh, st):
+    """The six backward launches of one layer (n > 0): dh written, the four
+    weight-gradient slabs filled."""
+    (h, q, k, v, attn, z, pre1, stats1, h1, r, bits, pre2, stats2,
+     wq, wk, wv, wo, g1, w1, w2, g2) = saved
+    n, dev = h.shape[0], h.device
+    new = lambda w: torch.empty(n, w, dtype=torch.float32, device=dev)
+    dp2, dr, dh1 = new(HIDDEN), new(GT_FFN), new(HIDDEN)
+    _lib.call("scgib_gt_ffn_bwd", _p(g), _p(pre2), _p(stats2), _p(g2), _p(r), _p(bits),
+              int(training), _p(h1), _p(w1), _p(w2), n, _p(dp2), _p(dr), _p(dh1),
+              _p(slabs[0]), _p(slabs[1]), _p(gr.dims), st)
+    dp1, dattn = new(HIDDEN), new(HIDDEN)
+    _lib.call("scgib_gt_out_bwd", _p(dh1), _p(pre1), _p(stats1), _p(g1), _p(attn), _p(wo),
+              n, _p(dp1), _p(dattn), _p(slabs[2]), _p(gr.dims), st)
+    dq, dk, dv = _gt_attn_bwd(dattn, attn, z, q, k, v, gr, heads)
+    _lib.call("scgib_gt_qkv_bwd", _p(dq), _p(dk), _p(dv), _p(h), _p(wq), _p(wk), _p(wv),
+              _p(dp1), n, _p(dh), _p(slabs[3]), _p(gr.dims), st)
+
+
+def _gt_grad_views(wg, woff):
+    """The 16 parameter gradients of a layer (``_GtLayer``'s order) as views of
+    its reduced weight-gradient row ``wg``."""
+    H, F2 = HIDDEN, GT_FFN
+    s0, s1, s2, s3 = (wg[woff[i]: woff[i + 1]] for i in range(_GT_SLABS))
+    dw2, db2, dg2, dbe2 = s0[:H * F2].view(H, F2), s0[H * F2: H * F2 + H], \
+        s0[H * F2 + H: H * F2 + 2 * H], s0[H * F2 + 2 * H:]
+    dw1, db1 = s1[:F2 * H].view(F2, H), s1[F2 * H:]
+    dwo, dbo, dg1, dbe1 = s2[:H * H].view(H, H), s2[H * H: H * H + H], \
+        s2[H * H + H: H * H + 2 * H], s2[H * H + 2 * H:]
+    dwq, dwk, dwv = (s3[i * H * H: (i + 1) * H * H].view(H, H) for i in range(3))
+    dbq, dbk, dbv = (s3[3 * H * H + i * H: 3 * H * H + (i + 1) * H] for i in range(3))
+    return (dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo, dg1, dbe1, dw1, db1, dw2, db2, dg2, dbe2)
+
+
 class _GtLayer(torch.autograd.Function):
     """One GraphTransformerLayer: five launches forward, six and one slab
     reduce backward.  params: Wq bq Wk bk Wv bv Wo bo g1 be1 W1 b1 W2 b2 g2 be2."""
@@ -2723,44 +2802,19 @@ class _GtLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, graph, heads, training, drop_mask, aux, *params):
         h = _f32(h, "gt_layer")
-        n, dev = h.shape[0], h.device
         P = [_f32(p, "gt_layer params") for p in params]
-        wq, bq, wk, bk, wv, bv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2 = P
-        st = _stream()
-        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
-        q, k, v = new(n, HIDDEN), new(n, HIDDEN), new(n, HIDDEN)
-        _lib.call("scgib_gt_qkv_fwd", _p(h), _p(wq), _p(bq), _p(wk), _p(bk), _p(wv), _p(bv), n,
-                  _p(q), _p(k), _p(v), _p(graph.dims), st)
-        attn, z, score = _gt_attn_fwd(q, k, v, graph, heads, aux is not None)
-        pre1, stats1, h1 = new(n, HIDDEN), new(n, 2), new(n, HIDDEN)
-        _lib.call("scgib_gt_out_fwd", _p(attn), _p(h), _p(wo), _p(bo), _p(g1), _p(be1), n,
-                  _p(pre1), _p(stats1), _p(h1), _p(graph.dims), st)
-        r, bits = new(n, GT_FFN), new(n, 4, dtype=torch.int32)
-        pos = new(n, 4, dtype=torch.int32) if aux is not None else None
-        keep = new(n, 4, dtype=torch.int32) if aux is not None else None
-        pre2, stats2, out = new(n, HIDDEN), new(n, 2), new(n, HIDDEN)
-        draw = training and drop_mask is None
-        rng = dropout_state(dev) if draw else None
-        cnt = counters(dev, "gt_dropout", 1) if draw else None
-        _lib.call("scgib_gt_ffn_fwd", _p(h1), _p(w1), _p(b1), _p(w2), _p(b2), _p(g2), _p(be2), n,
-                  int(training), _p(rng), _p(cnt), _p(drop_mask if training else None), _p(r),
-                  _p(bits), _p(pos), _p(keep), _p(pre2), _p(stats2), _p(out), _p(graph.dims), st)
-        if aux is not None:
-            aux["ffn_pos"], aux["keep"], aux["score"] = _unpack_bits(pos), _unpack_bits(keep), score
-        ctx.save_for_backward(h, q, k, v, attn, z, pre1, stats1, h1, r, bits, pre2, stats2,
-                              wq, wk, wv, wo, g1, w1, w2, g2)
+        out, saved = _gt_layer_fwd(h, graph, heads, training, drop_mask, aux, P, _stream())
+        ctx.save_for_backward(*saved)
         ctx.graph, ctx.heads, ctx.training = graph, heads, training
         return out
 
     @staticmethod
     def backward(ctx, g):
-        (h, q, k, v, attn, z, pre1, stats1, h1, r, bits, pre2, stats2,
-         wq, wk, wv, wo, g1, w1, w2, g2) = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        h = saved[0]
         g = _f32(g, "gt_layer.backward")
-        gr = ctx.graph
         n, dev = h.shape[0], h.device
-        widths = [int(_lib.query("scgib_gt_slab_width", i)) for i in range(_GT_SLABS)]
-        woff = [sum(widths[:i]) for i in range(_GT_SLABS + 1)]
+        widths, woff = _gt_slab_layout()
         wg = torch.zeros(woff[-1], dtype=torch.float32, device=dev)
         dh = torch.empty_like(h)
         if n:
@@ -2768,30 +2822,10 @@ class _GtLayer(torch.autograd.Function):
             slab = torch.empty(n_slabs * woff[-1], dtype=torch.float32, device=dev)
             slabs = [slab[n_slabs * woff[i]: n_slabs * woff[i + 1]] for i in range(_GT_SLABS)]
             st = _stream()
-            new = lambda w: torch.empty(n, w, dtype=torch.float32, device=dev)
-            dp2, dr, dh1 = new(HIDDEN), new(GT_FFN), new(HIDDEN)
-            _lib.call("scgib_gt_ffn_bwd", _p(g), _p(pre2), _p(stats2), _p(g2), _p(r), _p(bits),
-                      int(ctx.training), _p(h1), _p(w1), _p(w2), n, _p(dp2), _p(dr), _p(dh1),
-                      _p(slabs[0]), _p(slabs[1]), _p(gr.dims), st)
-            dp1, dattn = new(HIDDEN), new(HIDDEN)
-            _lib.call("scgib_gt_out_bwd", _p(dh1), _p(pre1), _p(stats1), _p(g1), _p(attn), _p(wo),
-                      n, _p(dp1), _p(dattn), _p(slabs[2]), _p(gr.dims), st)
-            dq, dk, dv = _gt_attn_bwd(dattn, attn, z, q, k, v, gr, ctx.heads)
-            _lib.call("scgib_gt_qkv_bwd", _p(dq), _p(dk), _p(dv), _p(h), _p(wq), _p(wk), _p(wv),
-                      _p(dp1), n, _p(dh), _p(slabs[3]), _p(gr.dims), st)
+            _gt_layer_bwd(g, saved, ctx.graph, ctx.heads, ctx.training, slabs, dh, st)
             _reduce_jobs([_lib.SlabJob(slabs[i].data_ptr(), wg[woff[i]:].data_ptr(), widths[i],
                                        n_slabs, 0) for i in range(_GT_SLABS)], st)
-        H, F2 = HIDDEN, GT_FFN
-        s0, s1, s2, s3 = (wg[woff[i]: woff[i + 1]] for i in range(_GT_SLABS))
-        dw2, db2, dg2, dbe2 = s0[:H * F2].view(H, F2), s0[H * F2: H * F2 + H], \
-            s0[H * F2 + H: H * F2 + 2 * H], s0[H * F2 + 2 * H:]
-        dw1, db1 = s1[:F2 * H].view(F2, H), s1[F2 * H:]
-        dwo, dbo, dg1, dbe1 = s2[:H * H].view(H, H), s2[H * H: H * H + H], \
-            s2[H * H + H: H * H + 2 * H], s2[H * H + 2 * H:]
-        dwq, dwk, dwv = (s3[i * H * H: (i + 1) * H * H].view(H, H) for i in range(3))
-        dbq, dbk, dbv = (s3[3 * H * H + i * H: 3 * H * H + (i + 1) * H] for i in range(3))
-        return (dh, None, None, None, None, None, dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo, dg1, dbe1,
-                dw1, db1, dw2, db2, dg2, dbe2)
+        return (dh, None, None, None, None, None, *_gt_grad_views(wg, woff))
 
 
 def gt_layer(h, graph, layer, drop_mask=None, return_aux=False):
@@ -2828,6 +2862,235 @@ def gt_encoder(h, graph, module, drop_masks=None):
     for i, layer in enumerate(module.layers):
         h = gt_layer(h, graph, layer, None if drop_masks is None else drop_masks[i])
     return h
+
+
+# The folded entry (csrc/gt_embed.hip): h0 = (x[node_map] Wt^T) We^T in one
+# launch — the raw features gathered in-kernel, transfer_d and embedding_h
+# folded — and the whole encoder as ONE autograd node behind it (gt_encoder_x),
+# the counterpart of gin_encoder_x.
+GT_EMBED_F_MAX = 16
+GT_TRANSFER = 32
+_GT_EMBED_WE = HIDDEN * GT_TRANSFER  # floats of dWe in the embed's slab row
+
+
+def _gt_embed_check(name, x, wt, we, node_map):
+    """Refusals of the folded entry; returns the number of output rows."""
+    for t in (x, wt, we) + (() if node_map is None else (node_map,)):
+        if not t.is_cuda:
+            raise _lib.ScgibError(f"{name}: tensor is on {t.device}; the S-CGIB ops run on the "
+                                  "HIP device only (no CPU fallback)")
+    if x.dim() != 2 or not 1 <= x.shape[1] <= GT_EMBED_F_MAX:
+        raise _lib.ScgibError(f"{name}: raw features {tuple(x.shape)} (the fold takes "
+                              f"[rows, F] with 1 <= F <= {GT_EMBED_F_MAX})")
+    if tuple(wt.shape) != (GT_TRANSFER, x.shape[1]) or tuple(we.shape) != (HIDDEN, GT_TRANSFER):
+        raise _lib.ScgibError(f"{name}: needs transfer_d.weight [{GT_TRANSFER}, {x.shape[1]}] and "
+                              f"embedding_h.weight [{HIDDEN}, {GT_TRANSFER}], got "
+                              f"{tuple(wt.shape)} / {tuple(we.shape)}")
+    if x.requires_grad:
+        raise _lib.ScgibError(f"{name}: no gradient w.r.t. the raw features")
+    if x.shape[0] == 0:
+        raise _lib.ScgibError(f"{name}: no feature rows")
+    if node_map is None:
+        return x.shape[0]
+    if node_map.dtype != torch.int32 or node_map.dim() != 1:
+        raise _lib.ScgibError(f"{name}: node_map must be an int32 vector")
+    return node_map.shape[0]
+
+
+def _gt_embed_fwd(x, wt, we, nmap, n, dims, st):
+    h0 = torch.empty(n, HIDDEN, dtype=torch.float32, device=x.device)
+    _lib.call("scgib_gt_embed_fwd", _p(x), x.shape[1], x.shape[0], _p(nmap), _p(wt), _p(we), n,
+              _p(h0), _p(dims), st)
+    return h0
+
+
+def _gt_embed_bwd(g, x, wt, we, nmap, dims, out, st):
+    """The embed's backward launch and its two reduce jobs: dWe | dWt land in
+    ``out`` (scgib_gt_embed_slab_width floats).  Returns (jobs, slab, dWe, dWt)."""
+    n, f = g.shape[0], x.shape[1]
+    width = int(_lib.query("scgib_gt_embed_slab_width", f))
+    ns = int(_lib.query("scgib_gt_embed_slabs", n))
+    slab = torch.empty(ns * width, dtype=torch.float32, device=g.device)
+    _lib.call("scgib_gt_embed_bwd", _p(g), _p(x), f, x.shape[0], _p(nmap), _p(wt), _p(we), n,
+              _p(slab), _p(dims), st)
+    jobs = [_lib.SlabJob(slab.data_ptr(), out.data_ptr(), _GT_EMBED_WE, ns, width),
+            _lib.SlabJob(slab.data_ptr() + 4 * _GT_EMBED_WE, out[_GT_EMBED_WE:].data_ptr(),
+                         GT_TRANSFER * f, ns, width)]
+    return jobs, slab, out[:_GT_EMBED_WE].view(HIDDEN, GT_TRANSFER), \
+        out[_GT_EMBED_WE:].view(GT_TRANSFER, f)
+
+
+class _GtEmbed(torch.autograd.Function):
+    """h0 = (x[nmap] Wt^T) We^T, one launch each way and one reduce."""
+
+    @staticmethod
+    def forward(ctx, x, wt, we, nmap, dims, n):
+        x, wt, we = (_f32(t, "gt_embed") for t in (x, wt, we))
+        h0 = _gt_embed_fwd(x, wt, we, nmap, n, dims, _stream())
+        ctx.save_for_backward(x, wt, we)
+        ctx.nmap, ctx.dims = nmap, dims
+        return h0
+
+    @staticmethod
+    def backward(ctx, g):
+        x, wt, we = ctx.saved_tensors
+        g = _f32(g, "gt_embed.backward")
+        width = int(_lib.query("scgib_gt_embed_slab_width", x.shape[1]))
+        if g.shape[0] == 0:
+            return None, torch.zeros_like(wt), torch.zeros_like(we), None, None, None
+        out = torch.empty(width, dtype=torch.float32, device=g.device)
+        st = _stream()
+        jobs, slab, dwe, dwt = _gt_embed_bwd(g, x, wt, we, ctx.nmap, ctx.dims, out, st)
+        _reduce_jobs(jobs, st)
+        del slab  # (allocated until the reduce is enqueued)
+        return None, dwt, dwe, None, None, None
+
+
+def gt_embed(x, transfer_weight, embedding_weight, node_map=None, dims=None):
+    """The Transformer encoder's folded entry alone: ``(x[node_map] Wt^T) We^T``
+    [N, 64] with Wt = ``transfer_weight`` [32, F] and We = ``embedding_weight``
+    [64, 32] (neither has a bias), F <= 16.  ``node_map`` (int32 [N]) maps the
+    output's rows to rows of ``x`` (None: the identity); ``dims`` (device int32,
+    capacity mode): rows >= dims[0] are zeros and take no part in the
+    gradients.  Differentiable in the two weights, not in ``x``."""
+    n = _gt_embed_check("gt_embed", x, transfer_weight, embedding_weight, node_map)
+    return _GtEmbed.apply(x, transfer_weight, embedding_weight, node_map, dims, n)
+
+
+class _GtEncoderX(torch.autograd.Function):
+    """A whole models.Transformer behind the folded entry as one autograd node:
+    forward the embed launch, five launches per layer and (``readout``) the
+    segment sums of the output; backward six launches per layer from the top
+    layer down, the embed's backward, and ONE fixed-order reduce of every
+    weight-gradient slab (4 per layer and the embed's 2 jobs).  The reduce
+    writes every element of every gradient it returns: no zero fill.
+    params: 16 per layer, _GtLayer's order."""
+
+    N_ARGS = 8  # inputs ahead of wt, we and the layer parameters
+
+    @staticmethod
+    def forward(ctx, x, graph, heads, training, drop_masks, nmap, readout, lane, wt, we, *params):
+        ctx.set_materialize_grads(False)
+        x, wt, we = (_f32(t, "gt_encoder_x") for t in (x, wt, we))
+        n, st = graph.num_nodes(), _stream()  # (the row capacity in capacity mode)
+        L = len(params) // 16
+        h = _gt_embed_fwd(x, wt, we, nmap, n, graph.dims, st)
+        saved = []
+        for l in range(L):
+            P = [_f32(p, "gt_encoder_x params") for p in params[16 * l: 16 * l + 16]]
+            h, sv = _gt_layer_fwd(h, graph, heads, training,
+                                  None if drop_masks is None else drop_masks[l], None, P, st, lane)
+            saved += sv
+        ro = None
+        if readout is not None:
+            ptr, nseg, seg_dims = readout
+            ro = torch.empty(int(nseg), HIDDEN, dtype=torch.float32, device=h.device)
+            _lib.call("scgib_segment_sum", _p(h), _p(ptr), int(nseg), HIDDEN, _p(ro), _p(seg_dims),
+                      st)
+        ctx.save_for_backward(x, wt, we, *saved)
+        ctx.graph, ctx.heads, ctx.training, ctx.L = graph, heads, training, L
+        ctx.nmap, ctx.readout = nmap, readout
+        return h if ro is None else (h, ro)
+
+    @staticmethod
+    def backward(ctx, g_out, g_readout=None):
+        t = ctx.saved_tensors
+        (x, wt, we), saved = t[:3], t[3:]
+        L, gr = ctx.L, ctx.graph
+        n, dev, st = saved[0].shape[0], saved[0].device, _stream()
+        none = (None,) * (_GtEncoderX.N_ARGS + 2 + 16 * L)
+        if g_readout is not None:  # the readout's adjoint: its row broadcast over the segment
+            ptr, nseg, seg_dims = ctx.readout
+            g = torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
+            g_readout = _f32(g_readout, "gt_encoder_x.backward readout")
+            _lib.call("scgib_segment_broadcast", _p(g_readout), _p(ptr), int(nseg), HIDDEN, _p(g),
+                      n, _p(seg_dims), st)
+            if g_out is not None:
+                g = g + _f32(g_out, "gt_encoder_x.backward")
+        elif g_out is not None:
+            g = _f32(g_out, "gt_encoder_x.backward")
+        else:  # neither output is used
+            return none
+        need = ctx.needs_input_grad[_GtEncoderX.N_ARGS:]
+        embed_need = bool(need[0] or need[1])
+        layer_need = [any(need[2 + 16 * l: 18 + 16 * l]) for l in range(L)]
+        # the chain stops at the lowest layer that has a trainable parameter
+        # (the fine-tune freezing quirk leaves only "layers.2" trainable)
+        lowest = 0 if embed_need else min((l for l in range(L) if layer_need[l]), default=L)
+        widths, woff = _gt_slab_layout()
+        lw = woff[-1]
+        ew = int(_lib.query("scgib_gt_embed_slab_width", x.shape[1])) if embed_need else 0
+        n_live = sum(layer_need[lowest:])
+        wg = torch.empty(n_live * lw + ew, dtype=torch.float32, device=dev)
+        n_slabs = int(_lib.query("scgib_gt_slabs", n))
+        jobs, keep, row = [], [], 0
+        grads = [None] * (16 * L)
+        for l in reversed(range(lowest, L)):
+            slab = torch.empty(n_slabs * lw, dtype=torch.float32, device=dev)
+            slabs = [slab[n_slabs * woff[i]: n_slabs * woff[i + 1]] for i in range(_GT_SLABS)]
+            dh = torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
+            _gt_layer_bwd(g, saved[_GT_SAVED * l: _GT_SAVED * (l + 1)], gr, ctx.heads,
+                          ctx.training, slabs, dh, st)
+            if layer_need[l]:  # (a frozen layer's slabs are written and never reduced)
+                out = wg[row * lw: (row + 1) * lw]
+                row += 1
+                jobs += [_lib.SlabJob(slabs[i].data_ptr(), out[woff[i]:].data_ptr(), widths[i],
+                                      n_slabs, 0) for i in range(_GT_SLABS)]
+                keep.append(slab)
+                grads[16 * l: 16 * l + 16] = _gt_grad_views(out, woff)
+            g = dh
+            slab = slabs = dh = None
+        dwt = dwe = None
+        if embed_need:
+            ejobs, eslab, dwe, dwt = _gt_embed_bwd(g, x, wt, we, ctx.nmap, gr.dims,
+                                                   wg[n_live * lw:], st)
+            jobs += ejobs
+            keep.append(eslab)
+        _reduce_jobs(jobs, st)
+        del keep  # slabs stay allocated until the launches are enqueued
+        return (*none[:_GtEncoderX.N_ARGS], dwt, dwe, *grads)
+
+
+def gt_encoder_x(x, graph, module, transfer, node_map=None, readout=None, drop_masks=None,
+                 lane=0):
+    """module(graph, transfer(x[node_map])) for a models.Transformer of width
+    64, as one autograd node on the folded entry (csrc/gt_embed.hip) and the
+    layer kernels of csrc/gt_layer.hip; the counterpart of gin_encoder_x.
+    ``x`` holds the raw normalised features of the parent rows (F <= 16, no
+    gradient); ``transfer`` is a Linear(F, 32, bias=False); ``node_map`` (int32)
+    maps the graph's rows to rows of ``x`` (ego batches: ego.ndata['_ID']).
+    ``readout`` = (ptr, nseg, seg_dims): also return the segment sums of the
+    output (ops.segment_sum's values) as a second result.  ``drop_masks``: one
+    explicit mask per layer (see gt_layer) instead of the device draw, which
+    in training mode comes from the dropout state of ``lane``."""
+    n = graph.num_nodes()
+    if n == 0:
+        raise _lib.ScgibError("gt_encoder_x on an empty graph")
+    if transfer.bias is not None:
+        raise _lib.ScgibError("gt_encoder_x: transfer_d fold needs Linear(F <= 16, 32, bias=False)")
+    we = module.embedding_h.weight
+    rows = _gt_embed_check("gt_encoder_x", x, transfer.weight, we, node_map)
+    if not graph.rowptr.is_cuda:
+        raise _lib.ScgibError("gt_encoder_x: the graph must be on the HIP device (no CPU fallback)")
+    if rows != n:
+        raise _lib.ScgibError(f"gt_encoder_x: {rows} rows for a graph of {n} nodes")
+    layers = list(module.layers)
+    heads = {int(layer.num_heads) for layer in layers}
+    if len(heads) != 1 or next(iter(heads)) not in GT_HEADS:
+        raise _lib.ScgibError(f"gt_encoder_x: num_heads {sorted(heads)} (supported: {GT_HEADS}, "
+                              "one value for every layer)")
+    training = bool(module.training)
+    if drop_masks is not None:
+        if len(drop_masks) != len(layers):
+            raise _lib.ScgibError(f"gt_encoder_x: {len(layers)} layers, {len(drop_masks)} masks")
+        for m in drop_masks:
+            if not m.is_cuda or m.dtype != torch.bool or tuple(m.shape) != (n, GT_FFN):
+                raise _lib.ScgibError(f"gt_encoder_x: drop_masks must be bool [{n}, {GT_FFN}] "
+                                      "tensors on the HIP device")
+        drop_masks = [m.contiguous() for m in drop_masks]
+    params = [p for layer in layers for p in layer.gt_params()]
+    return _GtEncoderX.apply(x, graph, heads.pop(), training, drop_masks, node_map, readout,
+                             int(lane), transfer.weight, we, *params)
 
 
 # ---------------------------------------------------------------------------
