@@ -577,6 +577,27 @@ int scgib_set2set_bwd(const float *x, const int32_t *graph_ptr, int64_t n_graphs
 int scgib_set2set_wgrad(const float *save, const float *dgates, int64_t n_graphs, int32_t dim,
                         int32_t n_iters, float *dw_ih, float *dw_hh, float *db_ih, float *db_hh,
                         scgib_stream_t stream);
+/* Two inputs xa, xb [*][dim] over the same graph_ptr and the same LSTM in one
+ * launch per direction (the pretraining step's readouts of the noisy and the
+ * plain graph features, models.py:686 / :718): 2 n_graphs workgroups,
+ * workgroup g + n_graphs * which reads input `which`.  out [2][n_graphs][2 dim];
+ * g_outa / g_outb [n_graphs][2 dim] each, either (not both) NULL for an output
+ * no loss reads (zero gradient); save holds scgib_set2set_save_floats(2 n_graphs, ...) floats
+ * and dgates 2 n_graphs * n_iters * 4 dim, input `which` in the half `which`
+ * of each.  Outputs and dxa / dxb (distinct buffers) carry the bits of two
+ * single-input calls.  The weight gradients are the sum over both halves in
+ * index order, formed in one pass: by scgib_set2set_bwd2 itself, or, with the
+ * four of them NULL, by scgib_set2set_wgrad called with 2 n_graphs. */
+int scgib_set2set_fwd2(const float *xa, const float *xb, const int32_t *graph_ptr,
+                       int64_t n_graphs, int32_t dim, int32_t n_iters, const float *w_ih,
+                       const float *b_ih, const float *w_hh, const float *b_hh, float *save,
+                       float *out, scgib_stream_t stream);
+int scgib_set2set_bwd2(const float *xa, const float *xb, const int32_t *graph_ptr,
+                       int64_t n_graphs, int32_t dim, int32_t n_iters, const float *w_ih,
+                       const float *w_hh, const float *save, const float *g_outa,
+                       const float *g_outb, float *dxa, float *dxb, int64_t n_rows,
+                       float *dgates, float *dw_ih, float *dw_hh, float *db_ih, float *db_hh,
+                       scgib_stream_t stream);
 
 /* ---- A6: per-segment readouts (dgl.sum_nodes) -------------------------------
  * out[s,:] = sum_{i in [ptr[s], ptr[s+1])} x[i,:]   (models.py:716, 725, 733)
@@ -867,6 +888,32 @@ int scgib_interaction_bwd(const float *g_im, const float *g_z1, const float *g_z
                           const float *logit, const float *stats, float *df, float *dt,
                           float *ds, float *pgrad, const float *g_klmean, int32_t pad_rows,
                           float *pgrad_total, scgib_stream_t stream);
+/* The same pair with the attention selectable (scgib_interaction_fwd / _bwd
+ * are use_att = 1).  use_att = 0 is the reference's useAtt = 0
+ * (models.py:726): im[:, 64:] is the s row itself, logit is not written and
+ * the softmax / z-bar constant slots of stats are zero; the backward gives
+ * ds = g_im[:, 64:] and writes zeros for dW_att / db_att in pgrad.  w_att and
+ * b_att are still required (not read).  A forward and its backward take the
+ * same use_att. */
+int scgib_interaction_fwd_v2(const float *f, const float *t, const float *s,
+                             const float *u_gate, const float *u_feat, const int32_t *graph_ptr,
+                             int64_t n_graphs, int64_t n_nodes, const float *bn_gamma,
+                             const float *bn_beta, const float *bn_running_mean,
+                             const float *bn_running_var, float bn_eps, int32_t training,
+                             const float *w2, const float *b2, const float *w_att,
+                             const float *b_att, float *im, float *z1, float *z2, float *lam,
+                             float *logit, float *stats, float *kl_tensor, float *kl_mean,
+                             int32_t pad_rows, int32_t use_att, scgib_stream_t stream);
+int scgib_interaction_bwd_v2(const float *g_im, const float *g_z1, const float *g_z2,
+                             const float *g_kl, const float *f, const float *t, const float *s,
+                             const float *u_feat, const int32_t *graph_ptr, int64_t n_graphs,
+                             int64_t n_nodes, const float *bn_gamma, const float *bn_beta,
+                             const float *bn_running_mean, const float *bn_running_var,
+                             float bn_eps, int32_t training, const float *w2,
+                             const float *w_att, const float *z1, const float *lam,
+                             const float *logit, const float *stats, float *df, float *dt,
+                             float *ds, float *pgrad, const float *g_klmean, int32_t pad_rows,
+                             float *pgrad_total, int32_t use_att, scgib_stream_t stream);
 
 /* ---- A12: adjacency reconstruction loss, Gram form ------------------------
  * loss = sum_{u,v} (<im_u, im_v> - A_uv)^2 / N
@@ -977,6 +1024,17 @@ int scgib_contrastive_fwd(const float *z1, const float *z2, int64_t n_graphs, fl
 int scgib_contrastive_bwd(const float *z1, const float *z2, int64_t n_graphs, float *workspace,
                           const float *g_loss, float *dz1, float *dz2, uint32_t *counters,
                           scgib_stream_t stream);
+/* The same at row width `width` = 64 (the entries above) or 128 (the Set2Set
+ * readouts, models.py:686 / :718); any other width: SCGIB_EUNSUPPORTED.  The
+ * workspace grows with the width (scgib_contrastive_workspace_floats_w);
+ * scgib_contrastive_counters does not depend on it. */
+int64_t scgib_contrastive_workspace_floats_w(int64_t n_graphs, int32_t width);
+int scgib_contrastive_fwd_w(const float *z1, const float *z2, int64_t n_graphs, int32_t width,
+                            float *workspace, float *loss, uint32_t *counters,
+                            scgib_stream_t stream);
+int scgib_contrastive_bwd_w(const float *z1, const float *z2, int64_t n_graphs, int32_t width,
+                            float *workspace, const float *g_loss, float *dz1, float *dz2,
+                            uint32_t *counters, scgib_stream_t stream);
 
 /* ---- A10 head: fused dense layers (exact-f32 MFMA tiles) -----------------
  * mlp2: out = relu(x W1^T + b1) W2^T + b2, x [N][d_in] (d_in 64 or 128),

@@ -24,6 +24,10 @@ SIGNATURES = {
     "scgib_set2set_bwd": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P,
                                          _P, _P, _P, _P, _P]),
     "scgib_set2set_wgrad": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
+    "scgib_set2set_fwd2": (ctypes.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                                          _P]),
+    "scgib_set2set_bwd2": (ctypes.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                                          _P, _I64, _P, _P, _P, _P, _P, _P]),
     "scgib_head_fwd": (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P,
                                       _P]),
     "scgib_head_bwd": (ctypes.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _I32, _I32, _P, _P,
@@ -100,6 +104,12 @@ SIGNATURES = {
     "scgib_interaction_fwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P,
                                              _F, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                              _P, _P, _I32, _P]),
+    "scgib_interaction_fwd_v2": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P,
+                                                _P, _F, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                _P, _P, _P, _I32, _I32, _P]),
+    "scgib_interaction_bwd_v2": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64,
+                                                _P, _P, _P, _P, _F, _I32, _P, _P, _P, _P, _P, _P,
+                                                _P, _P, _P, _P, _P, _I32, _P, _I32, _P]),
     "scgib_noise_uniform": (ctypes.c_int, [_P, _P, _I64, _P, _P, _P]),
     "scgib_bn_running_update": (ctypes.c_int, [_P, _P, _I64, _F, _P, _P, _P, _P]),
     "scgib_interaction_bwd": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P,
@@ -120,6 +130,9 @@ SIGNATURES = {
     "scgib_contrastive_counters": (_I64, [_I64]),
     "scgib_contrastive_fwd": (ctypes.c_int, [_P, _P, _I64, _P, _P, _P, _P]),
     "scgib_contrastive_bwd": (ctypes.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "scgib_contrastive_workspace_floats_w": (_I64, [_I64, _I32]),
+    "scgib_contrastive_fwd_w": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P]),
+    "scgib_contrastive_bwd_w": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "scgib_mlp2_slab_floats": (_I64, [_I64, _I32]),
     "scgib_mlp2_recon_slab_floats": (_I64, [_I64, _I32]),
     "scgib_mlp2_fwd": (ctypes.c_int, [_P, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),

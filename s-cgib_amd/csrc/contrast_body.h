@@ -27,6 +27,18 @@
 // The split partials cross workgroups through agent-scope stores/loads and
 // block_arrive (common.h): no L2 write-back fence.
 //
+// Width: the bodies are templates on the row width D (64: the sum readouts,
+// also inside the head MLP's launches; 128: the Set2Set readouts).  The LDS
+// row stride is D + 4, the similarity k loop runs over D / 4, a lane holds
+// D / 4 operand values, and the backward's weighted sums take D / 64 channel
+// blocks per wave.  Grid, split / arrival scheme and the fp64 mean do not
+// depend on D; D = 64 is the code as it was.  LDS per workgroup at D = 128:
+// forward 2 x 64 x 132 x 4 B = 66 KB, backward 66 KB + 13 KB of weights (D = 64:
+// 34 KB and 47 KB).  The 160 KB of a CU hold two such workgroups; the
+// backward's registers (the row's two operand sets, 64 values each) allow one
+// wave per SIMD, i.e. one workgroup per CU, where D = 64 has two.  The grid
+// at B = 512 is 32 row blocks x 8 splits = 256 workgroups, one per CU.
+//
 // Arrival counters: caller-provided, zero on entry, left zero on exit (the
 // last arriver resets them), so the launches replay from a HIP graph.
 #pragma once
@@ -36,7 +48,11 @@ namespace scgib {
 
 constexpr int CR = 16;   // rows per workgroup
 constexpr int CT = 64;   // column tile
-constexpr int CLD = 68;  // LDS row stride (16-byte aligned rows)
+constexpr int CLD = 68;  // LDS row stride at width 64 (16-byte aligned rows)
+constexpr int CWLD = 68; // row stride of the backward's weight blocks (16 x 64 columns)
+template <int D>
+constexpr int cld() { return D + 4; }  // LDS row stride at width D
+static_assert(cld<64>() == CLD, "width-64 stride");
 constexpr int kMaxSplit = 16;
 constexpr float kNormEps = 1e-12f;
 
@@ -51,40 +67,38 @@ __host__ __device__ inline int contrast_splits(int64_t B) {
 // the current one is computed on: tile_load (rows -> registers, rows >= B
 // zero), tile_store (normalise -> LDS).  256 threads: row tid >> 2, 16
 // channels per thread.
+// (width D: D / 16 float4 per thread, channels (D / 4) q ..)
+template <int D>
 struct TileRegs {
-    float4 v[4];
+    float4 v[D / 16];
 };
 
+template <int D>
 __device__ __forceinline__ void tile_load(const float *__restrict__ x, int64_t B, int64_t j0,
-                                          TileRegs &t) {
+                                          TileRegs<D> &t) {
+    constexpr int NV = D / 16;
     const int tid = threadIdx.x, r = tid >> 2, q = tid & 3;
     const int64_t j = j0 + r;
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-        t.v[k] = ld_ok(reinterpret_cast<const float4 *>(x), j * 16 + 4 * q + k, 4 * q + k, j < B,
-                       make_float4(0.f, 0.f, 0.f, 0.f));
+    for (int k = 0; k < NV; ++k)
+        t.v[k] = ld_ok(reinterpret_cast<const float4 *>(x), j * (D / 4) + NV * q + k, NV * q + k,
+                       j < B, make_float4(0.f, 0.f, 0.f, 0.f));
 }
 
-__device__ __forceinline__ void tile_store(const TileRegs &t, float *s) {
+template <int D>
+__device__ __forceinline__ void tile_store(const TileRegs<D> &t, float *s) {
+    constexpr int NV = D / 16;
     const int tid = threadIdx.x, r = tid >> 2, q = tid & 3;
     float ss = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) ss += t.v[k].x * t.v[k].x + t.v[k].y * t.v[k].y + t.v[k].z * t.v[k].z + t.v[k].w * t.v[k].w;
+    for (int k = 0; k < NV; ++k) ss += t.v[k].x * t.v[k].x + t.v[k].y * t.v[k].y + t.v[k].z * t.v[k].z + t.v[k].w * t.v[k].w;
     ss += __shfl_xor(ss, 1, kWave);
     ss += __shfl_xor(ss, 2, kWave);
     const float inv = 1.f / fmaxf(sqrtf(ss), kNormEps);
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-        *reinterpret_cast<float4 *>(s + r * CLD + 16 * q + 4 * k) =
+    for (int k = 0; k < NV; ++k)
+        *reinterpret_cast<float4 *>(s + r * cld<D>() + 4 * NV * q + 4 * k) =
             make_float4(t.v[k].x * inv, t.v[k].y * inv, t.v[k].z * inv, t.v[k].w * inv);
-}
-
-// Stage rows [j0, j0 + 64) of x, normalised, into s (64 x CLD); rows >= B are zero.
-__device__ __forceinline__ void stage_tile(const float *__restrict__ x, int64_t B, int64_t j0,
-                                           float *s) {
-    TileRegs t;
-    tile_load(x, B, j0, t);
-    tile_store(t, s);
 }
 
 // sum over the 16 lanes of a row group (lanes 16m .. 16m+15 of the wave)
@@ -95,33 +109,35 @@ __device__ __forceinline__ float sum16(float v) {
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kContrastBwdW = 3 * CR * CLD;
+constexpr int kContrastBwdW = 3 * CR * CWLD;
 
 __device__ __forceinline__ int kperm16(int s, int kq) { return 16 * (s >> 2) + 4 * kq + (s & 3); }
 __device__ __forceinline__ float f4c(const float4 &v, int t) {
     return t == 0 ? v.x : t == 1 ? v.y : t == 2 ? v.z : v.w;
 }
 
-// lane (row li, k quarter kq): the row's normalised values at kperm16(s, kq)
+// lane (row li, k quarter kq): the row's normalised values at kperm16(s, kq),
+// s < D / 4
+template <int D>
 __device__ __forceinline__ void load_row_k(const float *__restrict__ x, int64_t i, int64_t B,
-                                           int kq, float (&q)[16]) {
+                                           int kq, float (&q)[D / 4]) {
     const int64_t ic = i < B ? i : 0;
     const float m = i < B ? 1.f : 0.f;
-    float4 v[4];
+    float4 v[D / 16];
     float ss = 0.f;
 #pragma unroll
-    for (int mm = 0; mm < 4; ++mm) {
-        v[mm] = *reinterpret_cast<const float4 *>(x + ic * 64 + 16 * mm + 4 * kq);
+    for (int mm = 0; mm < D / 16; ++mm) {
+        v[mm] = *reinterpret_cast<const float4 *>(x + ic * D + 16 * mm + 4 * kq);
         ss += v[mm].x * v[mm].x + v[mm].y * v[mm].y + v[mm].z * v[mm].z + v[mm].w * v[mm].w;
     }
     ss += __shfl_xor(ss, 16, kWave);
     ss += __shfl_xor(ss, 32, kWave);
     const float inv = m / fmaxf(sqrtf(ss), kNormEps);
 #pragma unroll
-    for (int s = 0; s < 16; ++s) q[s] = f4c(v[s >> 2], s & 3) * inv;
+    for (int s = 0; s < D / 4; ++s) q[s] = f4c(v[s >> 2], s & 3) * inv;
 }
 
-// workspace (floats): D[B] | fwd partials [T][B][4] | bwd partials [S][B][128],
+// workspace (floats): D[B] | fwd partials [T][B][4] | bwd partials [S][B][2 D],
 // T = contrast_tiles(B), S = contrast_splits(B); a launch may use NS <= S splits.
 // The bodies take their workgroup's (row block bx, split by) and LDS buffers
 // from the caller, so a kernel of another op can run them in extra
@@ -144,27 +160,31 @@ __host__ __device__ inline int64_t contrast_row_blocks(int64_t B) { return (B + 
 __host__ __device__ inline int64_t contrast_tiles(int64_t B) { return (B + CT - 1) / CT; }
 // workspace offset of the backward's split partials (after D and the
 // forward's tile partials)
+// (width-independent: the split partials, 2 D floats per row and split, follow it)
 __host__ __device__ inline int64_t contrast_pb_offset(int64_t B) { return B + 4 * contrast_tiles(B) * B; }
 
-// forward body: sK1, sK2 >= CT * CLD floats each.  S11 = Q1 K1^T and
+// forward body: sK1, sK2 >= CT * cld<D>() floats each.  S11 = Q1 K1^T and
 // S12 = Q1 K2^T per 64-column tile on the f32 MFMA (as the backward: wave w
 // takes columns 16w.. of the tile, lanes hold rows 4 kq + r), their
 // exponentials summed per lane over the tiles, then over the 16 columns of
 // a wave (shuffles) and the 4 waves (LDS, fixed order).
+template <int D = 64>
 __device__ __forceinline__ void contrast_fwd_body(const ContrastArgs &a, int64_t bx, int by,
                                                   float *sK1, float *sK2) {
+    static_assert(D == 64 || D == 128, "contrastive width");
+    constexpr int LD = cld<D>();
     const float *__restrict__ z1 = a.z1, *__restrict__ z2 = a.z2;
     const int64_t B = a.B;
     float *__restrict__ ws = a.ws;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, li = l & 15, kq = l >> 4;
     const int NS = a.nsplit;
     const int64_t row0 = bx * CR;
-    float q1[16];
-    load_row_k(z1, row0 + li, B, kq, q1);
+    float q1[D / 4];
+    load_row_k<D>(z1, row0 + li, B, kq, q1);
     float *Dv = ws, *pf = ws + B;
     __shared__ float sPart[4][CR][4];
     const int64_t jstep = static_cast<int64_t>(NS) * CT;
-    TileRegs t1, t2;  // the next tile's rows, in flight during this tile
+    TileRegs<D> t1, t2;  // the next tile's rows, in flight during this tile
     if (static_cast<int64_t>(by) * CT < B) {
         tile_load(z1, B, static_cast<int64_t>(by) * CT, t1);
         tile_load(z2, B, static_cast<int64_t>(by) * CT, t2);
@@ -179,9 +199,9 @@ __device__ __forceinline__ void contrast_fwd_body(const ContrastArgs &a, int64_t
         }
         __syncthreads();
         f32x4 s11 = {0.f, 0.f, 0.f, 0.f}, s12 = s11;
-        const float *pk1 = sK1 + (16 * w + li) * CLD + 4 * kq, *pk2 = sK2 + (16 * w + li) * CLD + 4 * kq;
+        const float *pk1 = sK1 + (16 * w + li) * LD + 4 * kq, *pk2 = sK2 + (16 * w + li) * LD + 4 * kq;
 #pragma unroll
-        for (int mm = 0; mm < 4; ++mm) {
+        for (int mm = 0; mm < D / 16; ++mm) {
             const float4 b1 = *reinterpret_cast<const float4 *>(pk1 + 16 * mm);
             const float4 b2 = *reinterpret_cast<const float4 *>(pk2 + 16 * mm);
 #pragma unroll
@@ -250,9 +270,9 @@ __device__ __forceinline__ void contrast_fwd_body(const ContrastArgs &a, int64_t
                 sm[3] = fmaf(v[y].w, wy, sm[3]);
             }
         }
-        const float D = sm[0] + sm[1] - sm[2];
-        if (k < B) Dv[k] = D;
-        sRow[tid] = k < B ? static_cast<double>(-logf(sm[3] / D)) : 0.0;
+        const float Dk = sm[0] + sm[1] - sm[2];
+        if (k < B) Dv[k] = Dk;
+        sRow[tid] = k < B ? static_cast<double>(-logf(sm[3] / Dk)) : 0.0;
     }
     __syncthreads();
     if (tid == 0) {
@@ -278,7 +298,7 @@ __device__ __forceinline__ void contrast_fwd_body(const ContrastArgs &a, int64_t
     }
 }
 
-// backward body: sK1, sK2 >= CT * CLD floats, sWf >= 3 * CR * CLD, sDj unused.
+// backward body: sK1, sK2 >= CT * cld<D>() floats, sWf >= kContrastBwdW, sDj unused.
 //
 // The similarity blocks and the weighted sums are matrix products, run on
 // the f32 MFMA v_mfma_f32_16x16x4_f32 (wave w takes columns 16w.. of each
@@ -290,9 +310,12 @@ __device__ __forceinline__ void contrast_fwd_body(const ContrastArgs &a, int64_t
 // permuted identically for both operands, kperm16).  The earlier form (one
 // 64-long dependent VALU fma chain per dot product, one wave per SIMD inside
 // the head MLP's launch) took ~25 us per workgroup at B = 512 (phase trace).
+template <int D = 64>
 __device__ __forceinline__ void contrast_bwd_body(const ContrastArgs &a, int64_t bx, int by,
                                                   float *sK1, float *sK2, float *sWf,
                                                   float * /*sDj*/) {
+    static_assert(D == 64 || D == 128, "contrastive width");
+    constexpr int LD = cld<D>(), NC = D / 64;  // channel blocks of 64 per wave pass
     const float *__restrict__ z1 = a.z1, *__restrict__ z2 = a.z2;
     const int64_t B = a.B;
     const float *__restrict__ ws = a.ws;
@@ -304,19 +327,21 @@ __device__ __forceinline__ void contrast_bwd_body(const ContrastArgs &a, int64_t
     const float g = *a.g_loss / static_cast<float>(B);
     const float *Dv = ws;
     float *pb = a.ws + contrast_pb_offset(B);
-    float q1[16], q2[16];  // A operands: row row0 + li, k = kperm16(s, kq)
-    load_row_k(z1, row0 + li, B, kq, q1);
-    load_row_k(z2, row0 + li, B, kq, q2);
+    float q1[D / 4], q2[D / 4];  // A operands: row row0 + li, k = kperm16(s, kq)
+    load_row_k<D>(z1, row0 + li, B, kq, q1);
+    load_row_k<D>(z2, row0 + li, B, kq, q2);
     float invDi[4];        // output rows 4 kq + r
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int64_t i = row0 + 4 * kq + r;
         invDi[r] = i < B ? 1.f / Dv[i] : 0.f;
     }
-    float *sW = sWf;  // [3][CR][CLD]: W11, W12, W21
-    f32x4 d1 = {0.f, 0.f, 0.f, 0.f}, d2 = d1;  // rows 4 kq + r, channel 16 w + li
+    float *sW = sWf;  // [3][CR][CWLD]: W11, W12, W21
+    f32x4 d1[NC], d2[NC];  // rows 4 kq + r, channel 64 cb + 16 w + li
+#pragma unroll
+    for (int cb = 0; cb < NC; ++cb) d1[cb] = d2[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int64_t jstep = static_cast<int64_t>(NS) * CT;
-    TileRegs t1, t2;  // the next tile's rows, in flight during this tile
+    TileRegs<D> t1, t2;  // the next tile's rows, in flight during this tile
     if (static_cast<int64_t>(by) * CT < B) {
         tile_load(z1, B, static_cast<int64_t>(by) * CT, t1);
         tile_load(z2, B, static_cast<int64_t>(by) * CT, t2);
@@ -333,9 +358,9 @@ __device__ __forceinline__ void contrast_bwd_body(const ContrastArgs &a, int64_t
         }
         __syncthreads();
         f32x4 s11 = {0.f, 0.f, 0.f, 0.f}, s12 = s11, s21 = s11;
-        const float *pk1 = sK1 + (16 * w + li) * CLD + 4 * kq, *pk2 = sK2 + (16 * w + li) * CLD + 4 * kq;
+        const float *pk1 = sK1 + (16 * w + li) * LD + 4 * kq, *pk2 = sK2 + (16 * w + li) * LD + 4 * kq;
 #pragma unroll
-        for (int mm = 0; mm < 4; ++mm) {
+        for (int mm = 0; mm < D / 16; ++mm) {
             const float4 b1 = *reinterpret_cast<const float4 *>(pk1 + 16 * mm);
             const float4 b2 = *reinterpret_cast<const float4 *>(pk2 + 16 * mm);
 #pragma unroll
@@ -353,79 +378,106 @@ __device__ __forceinline__ void contrast_bwd_body(const ContrastArgs &a, int64_t
             const bool ok = i < B && j < B;
             const float delta = j == i ? 1.f : 0.f;
             const float e11 = expf(s11[r]), e12 = expf(s12[r]), e21 = expf(s21[r]);
-            const int o = (4 * kq + r) * CLD + 16 * w + li;
+            const int o = (4 * kq + r) * CWLD + 16 * w + li;
             sW[o] = ok && j != i ? g * e11 * (invDi[r] + invDj) : 0.f;
-            sW[CR * CLD + o] = ok ? g * (e12 * invDi[r] - delta) : 0.f;
-            sW[2 * CR * CLD + o] = ok ? g * (e21 * invDj - delta) : 0.f;
+            sW[CR * CWLD + o] = ok ? g * (e12 * invDi[r] - delta) : 0.f;
+            sW[2 * CR * CWLD + o] = ok ? g * (e21 * invDj - delta) : 0.f;
         }
         __syncthreads();
         // d1 += W11 K1 + W12 K2, d2 += W21 K1 over the tile's 64 columns j
-        const float *pw = sW + li * CLD + 4 * kq;
+        const float *pw = sW + li * CWLD + 4 * kq;
         const float *pc1 = sK1 + 16 * w + li, *pc2 = sK2 + 16 * w + li;
 #pragma unroll
         for (int mm = 0; mm < 4; ++mm) {
             const float4 w11 = *reinterpret_cast<const float4 *>(pw + 16 * mm);
-            const float4 w12 = *reinterpret_cast<const float4 *>(pw + CR * CLD + 16 * mm);
-            const float4 w21 = *reinterpret_cast<const float4 *>(pw + 2 * CR * CLD + 16 * mm);
+            const float4 w12 = *reinterpret_cast<const float4 *>(pw + CR * CWLD + 16 * mm);
+            const float4 w21 = *reinterpret_cast<const float4 *>(pw + 2 * CR * CWLD + 16 * mm);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int jj = kperm16(4 * mm + t, kq);
-                const float k1 = pc1[jj * CLD], k2 = pc2[jj * CLD];
-                d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(w11, t), k1, d1, 0, 0, 0);
-                d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(w21, t), k1, d2, 0, 0, 0);
-                d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(w12, t), k2, d1, 0, 0, 0);
+#pragma unroll
+                for (int cb = 0; cb < NC; ++cb) {
+                    const float k1 = pc1[jj * LD + 64 * cb], k2 = pc2[jj * LD + 64 * cb];
+                    d1[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(w11, t), k1, d1[cb], 0, 0, 0);
+                    d2[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(w21, t), k1, d2[cb], 0, 0, 0);
+                    d1[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(w12, t), k2, d1[cb], 0, 0, 0);
+                }
             }
         }
     }
-    // this split's partial rows -> [split][B][128] (d1 | d2)
+    // this split's partial rows -> [split][B][2 D] (d1 | d2)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int64_t i = row0 + 4 * kq + r;
         if (i < B) {
-            float *p = pb + (static_cast<int64_t>(by) * B + i) * 128 + 16 * w + li;
-            st_agent(p, d1[r]);
-            st_agent(p + 64, d2[r]);
+            float *p = pb + (static_cast<int64_t>(by) * B + i) * (2 * D) + 16 * w + li;
+#pragma unroll
+            for (int cb = 0; cb < NC; ++cb) {
+                st_agent(p + 64 * cb, d1[cb][r]);
+                st_agent(p + D + 64 * cb, d2[cb][r]);
+            }
         }
     }
     if (!block_arrive(counters + bx, NS)) return;
     // last split of the row block: fixed-order sum over the splits, then the
-    // normalisation backward; row r = tid >> 4, channels 4 cl .. 4 cl + 3
+    // normalisation backward; row r = tid >> 4, channels 64 cb + 4 cl .. + 3
     const int r = tid >> 4, cl = tid & 15;
     const int64_t i = row0 + r;
     if (i < B) {
-        float4 e1 = make_float4(0.f, 0.f, 0.f, 0.f), e2 = e1;
-        float4 v1[kMaxSplit], v2[kMaxSplit];
+        float4 e1[NC], e2[NC];
 #pragma unroll
-        for (int y = 0; y < kMaxSplit; ++y) {  // all splits in flight (clamped), summed in order
-            const float *p = pb + (static_cast<int64_t>(y < NS ? y : 0) * B + i) * 128 + 4 * cl;
-            v1[y] = ld_agent4(p);
-            v2[y] = ld_agent4(p + 64);
-        }
+        for (int cb = 0; cb < NC; ++cb) {
+            e1[cb] = e2[cb] = make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 v1[kMaxSplit], v2[kMaxSplit];
 #pragma unroll
-        for (int y = 0; y < kMaxSplit; ++y) {
-            const float wy = y < NS ? 1.f : 0.f;
-            e1.x = fmaf(v1[y].x, wy, e1.x); e1.y = fmaf(v1[y].y, wy, e1.y);
-            e1.z = fmaf(v1[y].z, wy, e1.z); e1.w = fmaf(v1[y].w, wy, e1.w);
-            e2.x = fmaf(v2[y].x, wy, e2.x); e2.y = fmaf(v2[y].y, wy, e2.y);
-            e2.z = fmaf(v2[y].z, wy, e2.z); e2.w = fmaf(v2[y].w, wy, e2.w);
+            for (int y = 0; y < kMaxSplit; ++y) {  // all splits in flight (clamped), summed in order
+                const float *p = pb + (static_cast<int64_t>(y < NS ? y : 0) * B + i) * (2 * D) + 64 * cb + 4 * cl;
+                v1[y] = ld_agent4(p);
+                v2[y] = ld_agent4(p + D);
+            }
+#pragma unroll
+            for (int y = 0; y < kMaxSplit; ++y) {
+                const float wy = y < NS ? 1.f : 0.f;
+                e1[cb].x = fmaf(v1[y].x, wy, e1[cb].x); e1[cb].y = fmaf(v1[y].y, wy, e1[cb].y);
+                e1[cb].z = fmaf(v1[y].z, wy, e1[cb].z); e1[cb].w = fmaf(v1[y].w, wy, e1[cb].w);
+                e2[cb].x = fmaf(v2[y].x, wy, e2[cb].x); e2[cb].y = fmaf(v2[y].y, wy, e2[cb].y);
+                e2[cb].z = fmaf(v2[y].z, wy, e2[cb].z); e2[cb].w = fmaf(v2[y].w, wy, e2[cb].w);
+            }
         }
         // this lane's channels of the normalised rows and the row norms
-        const float4 x1 = reinterpret_cast<const float4 *>(z1 + i * 64)[cl];
-        const float4 x2 = reinterpret_cast<const float4 *>(z2 + i * 64)[cl];
-        const float inv1 = 1.f / fmaxf(sqrtf(sum16(x1.x * x1.x + x1.y * x1.y + x1.z * x1.z + x1.w * x1.w)), kNormEps);
-        const float inv2 = 1.f / fmaxf(sqrtf(sum16(x2.x * x2.x + x2.y * x2.y + x2.z * x2.z + x2.w * x2.w)), kNormEps);
-        const float4 a1 = make_float4(x1.x * inv1, x1.y * inv1, x1.z * inv1, x1.w * inv1);
-        const float4 a2 = make_float4(x2.x * inv2, x2.y * inv2, x2.z * inv2, x2.w * inv2);
-        const float p1 = sum16(a1.x * e1.x + a1.y * e1.y + a1.z * e1.z + a1.w * e1.w);
-        const float p2 = sum16(a2.x * e2.x + a2.y * e2.y + a2.z * e2.z + a2.w * e2.w);
+        float4 x1[NC], x2[NC];
+        float n1 = 0.f, n2 = 0.f;
+#pragma unroll
+        for (int cb = 0; cb < NC; ++cb) {
+            x1[cb] = reinterpret_cast<const float4 *>(z1 + i * D + 64 * cb)[cl];
+            x2[cb] = reinterpret_cast<const float4 *>(z2 + i * D + 64 * cb)[cl];
+            n1 += x1[cb].x * x1[cb].x + x1[cb].y * x1[cb].y + x1[cb].z * x1[cb].z + x1[cb].w * x1[cb].w;
+            n2 += x2[cb].x * x2[cb].x + x2[cb].y * x2[cb].y + x2[cb].z * x2[cb].z + x2[cb].w * x2[cb].w;
+        }
+        const float inv1 = 1.f / fmaxf(sqrtf(sum16(n1)), kNormEps);
+        const float inv2 = 1.f / fmaxf(sqrtf(sum16(n2)), kNormEps);
+        float4 a1[NC], a2[NC];
+        float t1s = 0.f, t2s = 0.f;
+#pragma unroll
+        for (int cb = 0; cb < NC; ++cb) {
+            a1[cb] = make_float4(x1[cb].x * inv1, x1[cb].y * inv1, x1[cb].z * inv1, x1[cb].w * inv1);
+            a2[cb] = make_float4(x2[cb].x * inv2, x2[cb].y * inv2, x2[cb].z * inv2, x2[cb].w * inv2);
+            t1s += a1[cb].x * e1[cb].x + a1[cb].y * e1[cb].y + a1[cb].z * e1[cb].z + a1[cb].w * e1[cb].w;
+            t2s += a2[cb].x * e2[cb].x + a2[cb].y * e2[cb].y + a2[cb].z * e2[cb].z + a2[cb].w * e2[cb].w;
+        }
+        const float p1 = sum16(t1s);
+        const float p2 = sum16(t2s);
         const float s1 = inv1 < 1.f / kNormEps ? p1 : 0.f;  // |z| <= eps: z / eps, no projection
         const float s2 = inv2 < 1.f / kNormEps ? p2 : 0.f;
-        reinterpret_cast<float4 *>(dz1 + i * 64)[cl] =
-            make_float4((e1.x - a1.x * s1) * inv1, (e1.y - a1.y * s1) * inv1,
-                        (e1.z - a1.z * s1) * inv1, (e1.w - a1.w * s1) * inv1);
-        reinterpret_cast<float4 *>(dz2 + i * 64)[cl] =
-            make_float4((e2.x - a2.x * s2) * inv2, (e2.y - a2.y * s2) * inv2,
-                        (e2.z - a2.z * s2) * inv2, (e2.w - a2.w * s2) * inv2);
+#pragma unroll
+        for (int cb = 0; cb < NC; ++cb) {
+            reinterpret_cast<float4 *>(dz1 + i * D + 64 * cb)[cl] =
+                make_float4((e1[cb].x - a1[cb].x * s1) * inv1, (e1[cb].y - a1[cb].y * s1) * inv1,
+                            (e1[cb].z - a1[cb].z * s1) * inv1, (e1[cb].w - a1[cb].w * s1) * inv1);
+            reinterpret_cast<float4 *>(dz2 + i * D + 64 * cb)[cl] =
+                make_float4((e2[cb].x - a2[cb].x * s2) * inv2, (e2[cb].y - a2[cb].y * s2) * inv2,
+                            (e2[cb].z - a2[cb].z * s2) * inv2, (e2[cb].w - a2[cb].w * s2) * inv2);
+        }
     }
     if (tid == 0) counters[bx] = 0u;
 }

@@ -23,6 +23,12 @@
 // computing it costs one red16 per graph and keeps the parameter gradients
 // identical in exact arithmetic to the reference's.
 //
+// ATT = false (the reference's useAtt = 0, models.py:726): the interaction
+// map's second half is the raw s row, cat(noisy, sum_nodes(ego features)); no
+// logit, no softmax and none of their statistics are computed (the slots are
+// written as zeros), the backward passes g_im[:, 64:] through as ds and writes
+// the attention parameters' partials as zeros.  ATT = true is the code above.
+//
 // Latency-bound VALU/shuffle work (a few hundred FLOP per row): no MFMA.
 #include "common.h"
 #include "running_update.h"
@@ -224,7 +230,7 @@ __device__ __forceinline__ float wave_sum1(float v, float *sx, int w) {
     return v;
 }
 
-template <int NW>
+template <int NW, bool ATT>
 __global__ __launch_bounds__(64 * NW) void interaction_fwd_k(
     const float *__restrict__ f, const float *__restrict__ t, const float *__restrict__ s,
     const float *__restrict__ u_gate, const float *__restrict__ u_feat,
@@ -274,7 +280,7 @@ __global__ __launch_bounds__(64 * NW) void interaction_fwd_k(
     //   KL store pass for the last graph (lambda of the first chunk from
     //   registers, later chunks recomputed).
     const float4 f0 = ld4(f + r0 * 64 + L.ch), t0 = ld4(t + r0 * 64 + L.ch);
-    const float4 whi = ld4(watt + 64 + L.ch);
+    const float4 whi = ATT ? ld4(watt + 64 + L.ch) : f4(0.f);
     float4 acc6[6] = {f4(0.f), f4(0.f), f4(0.f), f4(0.f), f4(0.f), f4(0.f)};  // zf zt sf st qf qt
     float M = -INFINITY, S = 0.f;  // per row group, merged below
     float4 fk[CN], tk[CN], sk[CN];  // first chunk, kept
@@ -297,12 +303,14 @@ __global__ __launch_bounds__(64 * NW) void interaction_fwd_k(
             acc6[3] = macc(dt, wt, acc6[3]);
             acc6[4] = macc(df * df, wt, acc6[4]);
             acc6[5] = macc(dt * dt, wt, acc6[5]);
-            const float lg = red16(dot4(whi, sv[j]));
-            if (r < r1) {
-                if (L.c4 == 0) logit[r] = lg;
-                const float Mn = fmaxf(M, lg);
-                S = S * expf(M - Mn) + expf(lg - Mn);
-                M = Mn;
+            if constexpr (ATT) {
+                const float lg = red16(dot4(whi, sv[j]));
+                if (r < r1) {
+                    if (L.c4 == 0) logit[r] = lg;
+                    const float Mn = fmaxf(M, lg);
+                    S = S * expf(M - Mn) + expf(lg - Mn);
+                    M = Mn;
+                }
             }
         }
     };
@@ -323,14 +331,16 @@ __global__ __launch_bounds__(64 * NW) void interaction_fwd_k(
 #pragma unroll
     for (int i = 0; i < 6; ++i) acc6[i] = red_q4(acc6[i]);
     wave_sum4<NW>(acc6, sX, w, L.q, L.c4);
+    if constexpr (ATT) {
 #pragma unroll
-    for (int off = 16; off <= 32; off <<= 1) {  // merge the wave's four row groups' softmax
-        const float Mo = __shfl_xor(M, off, kWave), So = __shfl_xor(S, off, kWave);
-        const float Mn = fmaxf(M, Mo);
-        S = (S == 0.f ? 0.f : S * expf(M - Mn)) + (So == 0.f ? 0.f : So * expf(Mo - Mn));
-        M = Mn;
+        for (int off = 16; off <= 32; off <<= 1) {  // merge the wave's four row groups' softmax
+            const float Mo = __shfl_xor(M, off, kWave), So = __shfl_xor(S, off, kWave);
+            const float Mn = fmaxf(M, Mo);
+            S = (S == 0.f ? 0.f : S * expf(M - Mn)) + (So == 0.f ? 0.f : So * expf(Mo - Mn));
+            M = Mn;
+        }
     }
-    if constexpr (NW > 1) {  // ... and the waves', in wave order
+    if constexpr (ATT && NW > 1) {  // ... and the waves', in wave order
         if ((threadIdx.x & 63) == 0) {
             sM[w] = M;
             sS[w] = S;
@@ -347,7 +357,7 @@ __global__ __launch_bounds__(64 * NW) void interaction_fwd_k(
     }
     const float4 zf = acc6[0], zt = acc6[1], sf = acc6[2], st = acc6[3], qf = acc6[4], qt = acc6[5];
     SCGIB_MARK(2);
-    const float invS = 1.f / S;
+    const float invS = ATT ? 1.f / S : 0.f;
     const float inv_n = 1.f / n;
     const float4 mu = inv_n * zf, mt = inv_n * zt;
     // centred sums of squares (shifted formula); n == 1 -> 0 / 0 -> NaN std, as torch
@@ -399,11 +409,19 @@ __global__ __launch_bounds__(64 * NW) void interaction_fwd_k(
                 const float4 z = make_float4(d.x / se.x, d.y / se.y, d.z / se.z, d.w / se.w);
                 acc2[1] = macc(z * z, wt, acc2[1]);
             }
-            const float lg = red16(dot4(whi, sv[j]));
-            if (r < r1) {
-                st4(im + r * 128 + L.ch, nz);
-                st4(im + r * 128 + 64 + L.ch, (expf(lg - M) * invS) * sv[j]);
-                if (L.c4 == 0) lam[r] = lm;
+            if constexpr (ATT) {
+                const float lg = red16(dot4(whi, sv[j]));
+                if (r < r1) {
+                    st4(im + r * 128 + L.ch, nz);
+                    st4(im + r * 128 + 64 + L.ch, (expf(lg - M) * invS) * sv[j]);
+                    if (L.c4 == 0) lam[r] = lm;
+                }
+            } else {
+                if (r < r1) {
+                    st4(im + r * 128 + L.ch, nz);
+                    st4(im + r * 128 + 64 + L.ch, sv[j]);  // the raw s row
+                    if (L.c4 == 0) lam[r] = lm;
+                }
             }
         }
     };
@@ -427,7 +445,8 @@ __global__ __launch_bounds__(64 * NW) void interaction_fwd_k(
     if (qg == 0) st4(z1 + gi * 64 + L.ch, zacc);
     // the z-bar half of the attention logit (constant per graph; kept for the
     // record, the softmax above and its backward do not depend on it)
-    const float cst = red16(dot4(ld4(watt + L.ch), zacc)) + *battp;
+    float cst = 0.f;
+    if constexpr (ATT) cst = red16(dot4(ld4(watt + L.ch), zacc)) + *battp;
     // ---- KL of the last graph only, duplicated (models.py:657-659) ----
     if (last) {  // (block-uniform)
         const float4 den = se * se;
@@ -471,8 +490,8 @@ __global__ __launch_bounds__(64 * NW) void interaction_fwd_k(
         if (kl_mean && threadIdx.x == 0) *kl_mean = ksum / (static_cast<float>(n) * 64.f);
     }
     if (threadIdx.x == 0) {
-        sl[kStSoftMax] = M;
-        sl[kStSoftSum] = S;
+        sl[kStSoftMax] = ATT ? M : 0.f;
+        sl[kStSoftSum] = ATT ? S : 0.f;
         sl[kStConst] = cst;
     }
     SCGIB_MARK(5);
@@ -485,7 +504,7 @@ __global__ __launch_bounds__(1024) void bn_running_update_k(const scgib_running_
     running_update_body<1024>(a);
 }
 
-template <int NW>
+template <int NW, bool ATT>
 __global__ __launch_bounds__(64 * NW) void interaction_bwd_k(
     const float *__restrict__ g_im, const float *__restrict__ g_z1,
     const float *__restrict__ g_z2, const float *__restrict__ g_kl,
@@ -527,71 +546,90 @@ __global__ __launch_bounds__(64 * NW) void interaction_bwd_k(
     const float inv_n = 1.f / n;
     const float4 mt = ld4(sl + kStMeanT + L.ch), ssq = ld4(sl + kStSsqT + L.ch);
     const float4 mu = ld4(sl + kStMu + L.ch), sig = ld4(sl + kStSigma + L.ch);
-    const float M = sl[kStSoftMax], invS = 1.f / sl[kStSoftSum];
+    const float M = ATT ? sl[kStSoftMax] : 0.f, invS = ATT ? 1.f / sl[kStSoftSum] : 0.f;
     const float4 m_use = training ? mt : ld4(rmean + L.ch);
     const float4 v_use = training ? inv_n * ssq : ld4(rvar + L.ch);
     const float4 rstd = rcp_sqrt4(v_use + f4(bn_eps));
     const float4 gm = ld4(gamma + L.ch), bt = ld4(beta + L.ch), w2c = ld4(w2 + L.ch);
-    const float4 wlo = ld4(watt + L.ch), whi = ld4(watt + 64 + L.ch), zb = ld4(z1 + gi * 64 + L.ch);
+    const float4 wlo = ATT ? ld4(watt + L.ch) : f4(0.f), whi = ATT ? ld4(watt + 64 + L.ch) : f4(0.f);
+    const float4 zb = ATT ? ld4(z1 + gi * 64 + L.ch) : f4(0.f);
     SCGIB_MARK(1);
-
-    // ---- attention backward: a_v = alpha_v s_v, alpha = softmax(logit) ----
-    // The first chunk (all rows of a typical molecule's ego-net batch slice)
-    // stays in registers across the passes; later chunks are re-loaded.
-    auto att_load = [&](int64_t cb, float4 *ga, float4 *sv, float *lg) {
-#pragma unroll
-        for (int j = 0; j < CN; ++j) {
-            const int64_t r = cb + qg + RS * j, rr = r < r1 ? r : r0;
-            ga[j] = ld4(g_im + rr * 128 + 64 + L.ch);
-            sv[j] = ld4(s + rr * 64 + L.ch);
-            lg[j] = logit[rr];
-        }
-    };
-    float4 ga0[CN], sv0[CN];
-    float lg0[CN];
-    att_load(r0, ga0, sv0, lg0);
-    float sa = 0.f;  // sum alpha * dalpha of this row group (uniform over its lanes)
-    auto att_sum = [&](int64_t cb, const float4 *ga, const float4 *sv, const float *lg) {
-#pragma unroll
-        for (int j = 0; j < CN; ++j) {
-            const float da = red16(dot4(ga[j], sv[j]));
-            sa = fmaf(expf(lg[j] - M) * invS * da, cb + qg + RS * j < r1 ? 1.f : 0.f, sa);
-        }
-    };
-    att_sum(r0, ga0, sv0, lg0);
-    for (int64_t cb = r0 + RS * CN; cb < r1; cb += RS * CN) {
-        float4 ga[CN], sv[CN];
-        float lg[CN];
-        att_load(cb, ga, sv, lg);
-        att_sum(cb, ga, sv, lg);
-    }
-    const float SA = wave_sum1<NW>(red_q(sa), sK, wvi);
     float4 dwhi = f4(0.f);
-    float dcq = 0.f;
-    auto att_grad = [&](int64_t cb, const float4 *ga, const float4 *sv, const float *lg) {
+    float dc = 0.f;
+    if constexpr (!ATT) {
+        // no attention: a_v = s_v, so ds_v = g_im[v, 64:]; one load round per chunk
+        for (int64_t cb = r0; cb < r1; cb += RS * CN) {
+            float4 ga[CN];
 #pragma unroll
-        for (int j = 0; j < CN; ++j) {
-            const int64_t r = cb + qg + RS * j;
-            const float w = r < r1 ? 1.f : 0.f;
-            const float da = red16(dot4(ga[j], sv[j]));
-            const float al = expf(lg[j] - M) * invS;
-            const float dl = al * (da - SA);
-            if (r < r1) st4(ds + r * 64 + L.ch, al * ga[j] + dl * whi);
-            dwhi = macc(dl * sv[j], w, dwhi);
-            dcq = fmaf(dl, w, dcq);
+            for (int j = 0; j < CN; ++j) {
+                const int64_t r = cb + qg + RS * j, rr = r < r1 ? r : r0;
+                ga[j] = ld4(g_im + rr * 128 + 64 + L.ch);
+            }
+#pragma unroll
+            for (int j = 0; j < CN; ++j) {
+                const int64_t r = cb + qg + RS * j;
+                if (r < r1) st4(ds + r * 64 + L.ch, ga[j]);
+            }
         }
-    };
-    att_grad(r0, ga0, sv0, lg0);
-    for (int64_t cb = r0 + RS * CN; cb < r1; cb += RS * CN) {
-        float4 ga[CN], sv[CN];
-        float lg[CN];
-        att_load(cb, ga, sv, lg);
-        att_grad(cb, ga, sv, lg);
+    } else {
+
+        // ---- attention backward: a_v = alpha_v s_v, alpha = softmax(logit) ----
+        // The first chunk (all rows of a typical molecule's ego-net batch slice)
+        // stays in registers across the passes; later chunks are re-loaded.
+        auto att_load = [&](int64_t cb, float4 *ga, float4 *sv, float *lg) {
+#pragma unroll
+            for (int j = 0; j < CN; ++j) {
+                const int64_t r = cb + qg + RS * j, rr = r < r1 ? r : r0;
+                ga[j] = ld4(g_im + rr * 128 + 64 + L.ch);
+                sv[j] = ld4(s + rr * 64 + L.ch);
+                lg[j] = logit[rr];
+            }
+        };
+        float4 ga0[CN], sv0[CN];
+        float lg0[CN];
+        att_load(r0, ga0, sv0, lg0);
+        float sa = 0.f;  // sum alpha * dalpha of this row group (uniform over its lanes)
+        auto att_sum = [&](int64_t cb, const float4 *ga, const float4 *sv, const float *lg) {
+#pragma unroll
+            for (int j = 0; j < CN; ++j) {
+                const float da = red16(dot4(ga[j], sv[j]));
+                sa = fmaf(expf(lg[j] - M) * invS * da, cb + qg + RS * j < r1 ? 1.f : 0.f, sa);
+            }
+        };
+        att_sum(r0, ga0, sv0, lg0);
+        for (int64_t cb = r0 + RS * CN; cb < r1; cb += RS * CN) {
+            float4 ga[CN], sv[CN];
+            float lg[CN];
+            att_load(cb, ga, sv, lg);
+            att_sum(cb, ga, sv, lg);
+        }
+        const float SA = wave_sum1<NW>(red_q(sa), sK, wvi);
+        float dcq = 0.f;
+        auto att_grad = [&](int64_t cb, const float4 *ga, const float4 *sv, const float *lg) {
+#pragma unroll
+            for (int j = 0; j < CN; ++j) {
+                const int64_t r = cb + qg + RS * j;
+                const float w = r < r1 ? 1.f : 0.f;
+                const float da = red16(dot4(ga[j], sv[j]));
+                const float al = expf(lg[j] - M) * invS;
+                const float dl = al * (da - SA);
+                if (r < r1) st4(ds + r * 64 + L.ch, al * ga[j] + dl * whi);
+                dwhi = macc(dl * sv[j], w, dwhi);
+                dcq = fmaf(dl, w, dcq);
+            }
+        };
+        att_grad(r0, ga0, sv0, lg0);
+        for (int64_t cb = r0 + RS * CN; cb < r1; cb += RS * CN) {
+            float4 ga[CN], sv[CN];
+            float lg[CN];
+            att_load(cb, ga, sv, lg);
+            att_grad(cb, ga, sv, lg);
+        }
+        float4 dwv[1] = {red_q4(dwhi)};
+        wave_sum4<NW>(dwv, sX, wvi, L.q, L.c4);
+        dwhi = dwv[0];
+        dc = wave_sum1<NW>(red_q(dcq), sK, wvi);
     }
-    float4 dwv[1] = {red_q4(dwhi)};
-    wave_sum4<NW>(dwv, sX, wvi, L.q, L.c4);
-    dwhi = dwv[0];
-    const float dc = wave_sum1<NW>(red_q(dcq), sK, wvi);
     SCGIB_MARK(2);
     // (a NULL g_z1 / g_z2: the readouts feed no loss, e.g. in the fine-tune head)
     const float4 gb = (g_z1 ? ld4(g_z1 + gi * 64 + L.ch) : f4(0.f)) + dc * wlo;  // d z-bar -> every node's noisy
@@ -723,13 +761,14 @@ __global__ __launch_bounds__(64 * NW) void interaction_bwd_k(
 
 using namespace scgib;
 
-extern "C" int scgib_interaction_fwd(
+extern "C" int scgib_interaction_fwd_v2(
     const float *f, const float *t, const float *s, const float *u_gate, const float *u_feat,
     const int32_t *graph_ptr, int64_t n_graphs, int64_t n_nodes, const float *bn_gamma,
     const float *bn_beta, const float *bn_running_mean, const float *bn_running_var,
     float bn_eps, int32_t training, const float *w2, const float *b2, const float *w_att,
     const float *b_att, float *im, float *z1, float *z2, float *lam, float *logit,
-    float *stats, float *kl_tensor, float *kl_mean, int32_t pad_rows, scgib_stream_t stream) {
+    float *stats, float *kl_tensor, float *kl_mean, int32_t pad_rows, int32_t use_att,
+    scgib_stream_t stream) {
     if (n_graphs < 0 || n_nodes < 0) return SCGIB_EINVAL;
     if (n_graphs == 0) return SCGIB_OK;
     if (n_graphs > 0x7fffffff) return SCGIB_EUNSUPPORTED;
@@ -740,11 +779,30 @@ extern "C" int scgib_interaction_fwd(
         return SCGIB_EINVAL;
     if (!training && (!bn_running_mean || !bn_running_var)) return SCGIB_EINVAL;
     const unsigned grid = static_cast<unsigned>(n_graphs + (pad_rows ? 64 : 0));
-    interaction_fwd_k<kIntNW><<<dim3(grid), 64 * kIntNW, 0, as_stream(stream)>>>(
-        f, t, s, u_gate, u_feat, graph_ptr, n_graphs, bn_gamma, bn_beta, bn_running_mean,
-        bn_running_var, bn_eps, training, w2, b2, w_att, b_att, im, z1, z2, lam, logit, stats,
-        kl_tensor, kl_mean, n_nodes, pad_rows);
+    if (use_att)
+        interaction_fwd_k<kIntNW, true><<<dim3(grid), 64 * kIntNW, 0, as_stream(stream)>>>(
+            f, t, s, u_gate, u_feat, graph_ptr, n_graphs, bn_gamma, bn_beta, bn_running_mean,
+            bn_running_var, bn_eps, training, w2, b2, w_att, b_att, im, z1, z2, lam, logit, stats,
+            kl_tensor, kl_mean, n_nodes, pad_rows);
+    else
+        interaction_fwd_k<kIntNW, false><<<dim3(grid), 64 * kIntNW, 0, as_stream(stream)>>>(
+            f, t, s, u_gate, u_feat, graph_ptr, n_graphs, bn_gamma, bn_beta, bn_running_mean,
+            bn_running_var, bn_eps, training, w2, b2, w_att, b_att, im, z1, z2, lam, logit, stats,
+            kl_tensor, kl_mean, n_nodes, pad_rows);
     return launch_status();
+}
+
+extern "C" int scgib_interaction_fwd(
+    const float *f, const float *t, const float *s, const float *u_gate, const float *u_feat,
+    const int32_t *graph_ptr, int64_t n_graphs, int64_t n_nodes, const float *bn_gamma,
+    const float *bn_beta, const float *bn_running_mean, const float *bn_running_var,
+    float bn_eps, int32_t training, const float *w2, const float *b2, const float *w_att,
+    const float *b_att, float *im, float *z1, float *z2, float *lam, float *logit,
+    float *stats, float *kl_tensor, float *kl_mean, int32_t pad_rows, scgib_stream_t stream) {
+    return scgib_interaction_fwd_v2(f, t, s, u_gate, u_feat, graph_ptr, n_graphs, n_nodes,
+                                    bn_gamma, bn_beta, bn_running_mean, bn_running_var, bn_eps,
+                                    training, w2, b2, w_att, b_att, im, z1, z2, lam, logit, stats,
+                                    kl_tensor, kl_mean, pad_rows, 1, stream);
 }
 
 extern "C" int scgib_noise_uniform(float *u_gate, float *u_feat, int64_t n_rows,
@@ -773,14 +831,15 @@ extern "C" int scgib_bn_running_update(const float *stats, const int32_t *graph_
     return launch_status();
 }
 
-extern "C" int scgib_interaction_bwd(
+extern "C" int scgib_interaction_bwd_v2(
     const float *g_im, const float *g_z1, const float *g_z2, const float *g_kl, const float *f,
     const float *t, const float *s, const float *u_feat, const int32_t *graph_ptr,
     int64_t n_graphs, int64_t n_nodes, const float *bn_gamma, const float *bn_beta,
     const float *bn_running_mean, const float *bn_running_var, float bn_eps, int32_t training,
     const float *w2, const float *w_att, const float *z1, const float *lam,
     const float *logit, const float *stats, float *df, float *dt, float *ds, float *pgrad,
-    const float *g_klmean, int32_t pad_rows, float *pgrad_total, scgib_stream_t stream) {
+    const float *g_klmean, int32_t pad_rows, float *pgrad_total, int32_t use_att,
+    scgib_stream_t stream) {
     if (n_graphs < 0 || n_nodes < 0) return SCGIB_EINVAL;
     if (n_graphs == 0) return SCGIB_OK;
     if (n_graphs > 0x7fffffff) return SCGIB_EUNSUPPORTED;
@@ -791,10 +850,16 @@ extern "C" int scgib_interaction_bwd(
         return SCGIB_EINVAL;
     if (!training && (!bn_running_mean || !bn_running_var)) return SCGIB_EINVAL;
     const unsigned grid = static_cast<unsigned>(n_graphs + (pad_rows ? 64 : 0));
-    interaction_bwd_k<kIntNW><<<dim3(grid), 64 * kIntNW, 0, as_stream(stream)>>>(
-        g_im, g_z1, g_z2, g_kl, f, t, s, u_feat, graph_ptr, n_graphs, bn_gamma, bn_beta,
-        bn_running_mean, bn_running_var, bn_eps, training, w2, w_att, z1, lam, logit, stats,
-        df, dt, ds, pgrad, g_klmean, n_nodes);
+    if (use_att)
+        interaction_bwd_k<kIntNW, true><<<dim3(grid), 64 * kIntNW, 0, as_stream(stream)>>>(
+            g_im, g_z1, g_z2, g_kl, f, t, s, u_feat, graph_ptr, n_graphs, bn_gamma, bn_beta,
+            bn_running_mean, bn_running_var, bn_eps, training, w2, w_att, z1, lam, logit, stats,
+            df, dt, ds, pgrad, g_klmean, n_nodes);
+    else
+        interaction_bwd_k<kIntNW, false><<<dim3(grid), 64 * kIntNW, 0, as_stream(stream)>>>(
+            g_im, g_z1, g_z2, g_kl, f, t, s, u_feat, graph_ptr, n_graphs, bn_gamma, bn_beta,
+            bn_running_mean, bn_running_var, bn_eps, training, w2, w_att, z1, lam, logit, stats,
+            df, dt, ds, pgrad, g_klmean, n_nodes);
     if (pgrad_total) {
         const int rc = launch_status();
         if (rc != SCGIB_OK) return rc;
@@ -802,6 +867,20 @@ extern "C" int scgib_interaction_bwd(
                                   pgrad_total, as_stream(stream));
     }
     return launch_status();
+}
+
+extern "C" int scgib_interaction_bwd(
+    const float *g_im, const float *g_z1, const float *g_z2, const float *g_kl, const float *f,
+    const float *t, const float *s, const float *u_feat, const int32_t *graph_ptr,
+    int64_t n_graphs, int64_t n_nodes, const float *bn_gamma, const float *bn_beta,
+    const float *bn_running_mean, const float *bn_running_var, float bn_eps, int32_t training,
+    const float *w2, const float *w_att, const float *z1, const float *lam,
+    const float *logit, const float *stats, float *df, float *dt, float *ds, float *pgrad,
+    const float *g_klmean, int32_t pad_rows, float *pgrad_total, scgib_stream_t stream) {
+    return scgib_interaction_bwd_v2(g_im, g_z1, g_z2, g_kl, f, t, s, u_feat, graph_ptr, n_graphs,
+                                    n_nodes, bn_gamma, bn_beta, bn_running_mean, bn_running_var,
+                                    bn_eps, training, w2, w_att, z1, lam, logit, stats, df, dt,
+                                    ds, pgrad, g_klmean, pad_rows, pgrad_total, 1, stream);
 }
 
 #ifdef SCGIB_TRACE

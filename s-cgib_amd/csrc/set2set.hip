@@ -24,6 +24,12 @@
 // The backward (one workgroup per graph, rounds in reverse) writes the gates'
 // pre-activation gradients dG [B][T][4d]; set2set_wgrad_k then forms
 // dW_ih = dG^T q*_prev, dW_hh = dG^T h_prev and db = sum dG (fixed order).
+//
+// Two inputs over the same graphs and the same LSTM (scgib_set2set_fwd2 /
+// _bwd2: the pretraining step's two Set2Set readouts): 2 B workgroups,
+// workgroup g + B which reads input `which`; out, save and dG are indexed by
+// the workgroup, so each input has its own range ([2][B] ...) and the one
+// set2set_wgrad_k pass over R = 2 B T rounds sums both ranges in order.
 // Latency-bound VALU/shuffle work: no MFMA.
 #include "common.h"
 
@@ -360,16 +366,19 @@ __device__ __forceinline__ float s2s_dot_reg(const float4 (&w)[N4], const float 
 // every later round's dots read them there instead of reloading the rows.
 template <bool REG>
 __global__ __launch_bounds__(256) void set2set_fwd_k(
-    const float *__restrict__ x, const int32_t *__restrict__ ptr, int d, int T,
+    const float *__restrict__ xa, const float *__restrict__ xb, int64_t nB,
+    const int32_t *__restrict__ ptr, int d, int T,
     const float *__restrict__ w_ih, const float *__restrict__ b_ih,
     const float *__restrict__ w_hh, const float *__restrict__ b_hh, float *__restrict__ save,
     float *__restrict__ out) {
     __shared__ float sQ[2 * kS2SMaxD], sH[kS2SMaxD], sC[kS2SMaxD], sA[4 * kS2SMaxD];
     __shared__ float sX[kS2SRows * kS2SMaxD], sRedA[kS2SRed];
-    const int64_t g = blockIdx.x;
+    // workgroup g: graph gs of input xa (g < nB) or xb (block-uniform)
+    const int64_t g = blockIdx.x, gs = g < nB ? g : g - nB;
+    const float *__restrict__ x = g < nB ? xa : xb;
     const int tid = threadIdx.x, D2 = 2 * d, G4 = 4 * d, S = s2s_save(d);
     constexpr int NI = REG ? 2 * kS2SMaxD / 4 : 1, NH = REG ? kS2SMaxD / 4 : 1;
-    const int64_t p0 = ptr[g], p1 = ptr[g + 1];
+    const int64_t p0 = ptr[gs], p1 = ptr[gs + 1];
     const S2SRows X{x, sX, p0, s2s_stage(x, p0, p1, d, sX), d};
     float4 wi[NI], wh[NH];
     if constexpr (REG) {  // d = 64, G4 = 256: every thread owns a gate
@@ -442,21 +451,30 @@ __global__ __launch_bounds__(256) void set2set_fwd_k(
 // trace r05_s2s).
 template <bool REG>
 __global__ __launch_bounds__(256) void set2set_bwd_k(
-    const float *__restrict__ x, const int32_t *__restrict__ ptr, int64_t nseg, int d, int T,
+    const float *__restrict__ xa, const float *__restrict__ xb, int64_t nB,
+    const int32_t *__restrict__ ptr, int64_t nseg, int d, int T,
     const float *__restrict__ w_ih, const float *__restrict__ w_hh,
-    const float *__restrict__ save, const float *__restrict__ g_out, float *__restrict__ dx,
+    const float *__restrict__ save, const float *__restrict__ g_outa,
+    const float *__restrict__ g_outb, float *__restrict__ dxa, float *__restrict__ dxb,
     float *__restrict__ dG, int64_t nrows) {
+    // nseg workgroups of graphs (nB, or 2 nB with a second input), then padding
     if (static_cast<int64_t>(blockIdx.x) >= nseg) {  // block-uniform: the padding rows
-        const int64_t r0 = ptr[nseg], nb = gridDim.x - nseg;
+        const int64_t r0 = ptr[nB], nb = gridDim.x - nseg;
         for (int64_t i = r0 * d + (blockIdx.x - nseg) * 256 + threadIdx.x; i < nrows * d;
-             i += nb * 256)
-            dx[i] = 0.f;
+             i += nb * 256) {
+            dxa[i] = 0.f;
+            if (nseg > nB) dxb[i] = 0.f;
+        }
         return;
     }
     __shared__ float sDQ[2 * kS2SMaxD], sDH[kS2SMaxD], sDC[kS2SMaxD], sDG[4 * kS2SMaxD];
     __shared__ float sHq[kS2SMaxD], sAtt[kS2SMaxD], sPart[4][3 * kS2SMaxD];
     __shared__ float sX[kS2SRows * kS2SMaxD], sDX[kS2SRows * kS2SMaxD], sRedA[kS2SRed];
-    const int64_t g = blockIdx.x;
+    const int64_t g = blockIdx.x, gs = g < nB ? g : g - nB;
+    const float *__restrict__ x = g < nB ? xa : xb;
+    float *__restrict__ dx = g < nB ? dxa : dxb;
+    // d out of this input, [nB][2d]; NULL: an output no loss reads (zero)
+    const float *__restrict__ g_out = g < nB ? g_outa : g_outb;
     const int tid = threadIdx.x, D2 = 2 * d, G4 = 4 * d, S = s2s_save(d);
     // a round's saved values this thread reads (its act / c / c_prev slice,
     // the attention's max and denominator), loaded one round ahead — the last
@@ -472,7 +490,7 @@ __global__ __launch_bounds__(256) void set2set_bwd_k(
                        sv[8 * d + k], sv[3 * d + k], sv[9 * d], sv[9 * d + 1]};
     };
     SvRound cur = sv_load(T - 1);
-    const int64_t p0 = ptr[g], p1 = ptr[g + 1];
+    const int64_t p0 = ptr[gs], p1 = ptr[gs + 1];
     const S2SRows X{x, sX, p0, s2s_stage(x, p0, p1, d, sX), d};
     float wT[REG ? kS2SMaxD : 1][3];
     if constexpr (REG) {
@@ -487,7 +505,7 @@ __global__ __launch_bounds__(256) void set2set_bwd_k(
             }
         }
     }
-    if (tid < D2) sDQ[tid] = g_out[g * D2 + tid];
+    if (tid < D2) sDQ[tid] = g_out ? g_out[gs * D2 + tid] : 0.f;
     if (tid < d) sDH[tid] = sDC[tid] = 0.f;  // from round t + 1 (none after the last)
     SCGIB_MARK(0);
     __syncthreads();
@@ -629,21 +647,76 @@ extern "C" int64_t scgib_set2set_save_floats(int64_t n_graphs, int32_t dim, int3
     return n_graphs * n_iters * s2s_save(dim);
 }
 
+// nin = 1 (xb, dxb unused) or 2 inputs
+static int s2s_launch_fwd(const float *xa, const float *xb, int nin, const int32_t *graph_ptr,
+                          int64_t n_graphs, int32_t dim, int32_t n_iters, const float *w_ih,
+                          const float *b_ih, const float *w_hh, const float *b_hh, float *save,
+                          float *out, scgib_stream_t stream) {
+    if (n_graphs < 0 || dim < 1 || dim > kS2SMaxD || n_iters < 1) return SCGIB_EINVAL;
+    if (n_graphs == 0) return SCGIB_OK;
+    if (nin * n_graphs > 0x7fffffff) return SCGIB_EUNSUPPORTED;
+    if (!xa || !xb || !graph_ptr || !w_ih || !b_ih || !w_hh || !b_hh || !save || !out)
+        return SCGIB_EINVAL;
+    const unsigned grid = static_cast<unsigned>(nin * n_graphs);
+    if (dim == kS2SMaxD)
+        set2set_fwd_k<true><<<grid, 256, 0, as_stream(stream)>>>(
+            xa, xb, n_graphs, graph_ptr, dim, n_iters, w_ih, b_ih, w_hh, b_hh, save, out);
+    else
+        set2set_fwd_k<false><<<grid, 256, 0, as_stream(stream)>>>(
+            xa, xb, n_graphs, graph_ptr, dim, n_iters, w_ih, b_ih, w_hh, b_hh, save, out);
+    return launch_status();
+}
+
+static int s2s_launch_bwd(const float *xa, const float *xb, int nin, const int32_t *graph_ptr,
+                          int64_t n_graphs, int32_t dim, int32_t n_iters, const float *w_ih,
+                          const float *w_hh, const float *save, const float *g_outa,
+                          const float *g_outb, float *dxa, float *dxb, int64_t n_rows,
+                          float *dgates, float *dw_ih, float *dw_hh, float *db_ih, float *db_hh,
+                          scgib_stream_t stream) {
+    if (n_graphs < 0 || dim < 1 || dim > kS2SMaxD || n_iters < 1 || n_rows < 0)
+        return SCGIB_EINVAL;
+    if (n_graphs == 0) return SCGIB_OK;
+    if (nin * n_graphs > 0x7fffff00) return SCGIB_EUNSUPPORTED;
+    // the four weight gradients all NULL: the data gradient only (dgates kept
+    // for a later scgib_set2set_wgrad)
+    const bool wg = dw_ih || dw_hh || db_ih || db_hh;
+    if (!xa || !xb || !graph_ptr || !w_ih || !w_hh || !save || (!g_outa && !g_outb) || !dxa ||
+        !dxb || !dgates || (wg && (!dw_ih || !dw_hh || !db_ih || !db_hh)))
+        return SCGIB_EINVAL;
+    hipStream_t st = as_stream(stream);
+    const int64_t nseg = nin * n_graphs;
+    const int64_t tail = (n_rows * dim + 256 * 16 - 1) / (256 * 16);  // padding-zero blocks
+    const int64_t extra = tail < 1 ? 1 : (tail > 256 ? 256 : tail);
+    if (dim == kS2SMaxD)
+        set2set_bwd_k<true><<<static_cast<unsigned>(nseg + extra), 256, 0, st>>>(
+            xa, xb, n_graphs, graph_ptr, nseg, dim, n_iters, w_ih, w_hh, save, g_outa, g_outb,
+            dxa, dxb, dgates, n_rows);
+    else
+        set2set_bwd_k<false><<<static_cast<unsigned>(nseg + extra), 256, 0, st>>>(
+            xa, xb, n_graphs, graph_ptr, nseg, dim, n_iters, w_ih, w_hh, save, g_outa, g_outb,
+            dxa, dxb, dgates, n_rows);
+    int rc = launch_status();
+    if (rc != SCGIB_OK || !wg) return rc;
+    set2set_wgrad_k<<<static_cast<unsigned>(3 * dim + 1), 256, 0, st>>>(
+        save, dgates, nseg * n_iters, dim, dw_ih, dw_hh, db_ih, db_hh);
+    return launch_status();
+}
+
 extern "C" int scgib_set2set_fwd(const float *x, const int32_t *graph_ptr, int64_t n_graphs,
                                  int32_t dim, int32_t n_iters, const float *w_ih,
                                  const float *b_ih, const float *w_hh, const float *b_hh,
                                  float *save, float *out, scgib_stream_t stream) {
-    if (n_graphs < 0 || dim < 1 || dim > kS2SMaxD || n_iters < 1) return SCGIB_EINVAL;
-    if (n_graphs == 0) return SCGIB_OK;
-    if (!x || !graph_ptr || !w_ih || !b_ih || !w_hh || !b_hh || !save || !out)
-        return SCGIB_EINVAL;
-    if (dim == kS2SMaxD)
-        set2set_fwd_k<true><<<static_cast<unsigned>(n_graphs), 256, 0, as_stream(stream)>>>(
-            x, graph_ptr, dim, n_iters, w_ih, b_ih, w_hh, b_hh, save, out);
-    else
-        set2set_fwd_k<false><<<static_cast<unsigned>(n_graphs), 256, 0, as_stream(stream)>>>(
-            x, graph_ptr, dim, n_iters, w_ih, b_ih, w_hh, b_hh, save, out);
-    return launch_status();
+    return s2s_launch_fwd(x, x, 1, graph_ptr, n_graphs, dim, n_iters, w_ih, b_ih, w_hh, b_hh,
+                          save, out, stream);
+}
+
+extern "C" int scgib_set2set_fwd2(const float *xa, const float *xb, const int32_t *graph_ptr,
+                                  int64_t n_graphs, int32_t dim, int32_t n_iters,
+                                  const float *w_ih, const float *b_ih, const float *w_hh,
+                                  const float *b_hh, float *save, float *out,
+                                  scgib_stream_t stream) {
+    return s2s_launch_fwd(xa, xb, 2, graph_ptr, n_graphs, dim, n_iters, w_ih, b_ih, w_hh, b_hh,
+                          save, out, stream);
 }
 
 extern "C" int scgib_set2set_bwd(const float *x, const int32_t *graph_ptr, int64_t n_graphs,
@@ -652,29 +725,21 @@ extern "C" int scgib_set2set_bwd(const float *x, const int32_t *graph_ptr, int64
                                  float *dx, int64_t n_rows, float *dgates, float *dw_ih,
                                  float *dw_hh, float *db_ih, float *db_hh,
                                  scgib_stream_t stream) {
-    if (n_graphs < 0 || dim < 1 || dim > kS2SMaxD || n_iters < 1 || n_rows < 0)
-        return SCGIB_EINVAL;
-    if (n_graphs == 0) return SCGIB_OK;
-    // the four weight gradients all NULL: the data gradient only (dgates kept
-    // for a later scgib_set2set_wgrad)
-    const bool wg = dw_ih || dw_hh || db_ih || db_hh;
-    if (!x || !graph_ptr || !w_ih || !w_hh || !save || !g_out || !dx || !dgates ||
-        (wg && (!dw_ih || !dw_hh || !db_ih || !db_hh)))
-        return SCGIB_EINVAL;
-    hipStream_t st = as_stream(stream);
-    const int64_t tail = (n_rows * dim + 256 * 16 - 1) / (256 * 16);  // padding-zero blocks
-    const int64_t extra = tail < 1 ? 1 : (tail > 256 ? 256 : tail);
-    if (dim == kS2SMaxD)
-        set2set_bwd_k<true><<<static_cast<unsigned>(n_graphs + extra), 256, 0, st>>>(
-            x, graph_ptr, n_graphs, dim, n_iters, w_ih, w_hh, save, g_out, dx, dgates, n_rows);
-    else
-        set2set_bwd_k<false><<<static_cast<unsigned>(n_graphs + extra), 256, 0, st>>>(
-            x, graph_ptr, n_graphs, dim, n_iters, w_ih, w_hh, save, g_out, dx, dgates, n_rows);
-    int rc = launch_status();
-    if (rc != SCGIB_OK || !wg) return rc;
-    set2set_wgrad_k<<<static_cast<unsigned>(3 * dim + 1), 256, 0, st>>>(
-        save, dgates, n_graphs * n_iters, dim, dw_ih, dw_hh, db_ih, db_hh);
-    return launch_status();
+    return s2s_launch_bwd(x, x, 1, graph_ptr, n_graphs, dim, n_iters, w_ih, w_hh, save, g_out,
+                          g_out, dx, dx, n_rows, dgates, dw_ih, dw_hh, db_ih, db_hh, stream);
+}
+
+extern "C" int scgib_set2set_bwd2(const float *xa, const float *xb, const int32_t *graph_ptr,
+                                  int64_t n_graphs, int32_t dim, int32_t n_iters,
+                                  const float *w_ih, const float *w_hh, const float *save,
+                                  const float *g_outa, const float *g_outb, float *dxa,
+                                  float *dxb, int64_t n_rows,
+                                  float *dgates, float *dw_ih, float *dw_hh, float *db_ih,
+                                  float *db_hh, scgib_stream_t stream) {
+    if (dxa && dxa == dxb) return SCGIB_EINVAL;
+    return s2s_launch_bwd(xa, xb, 2, graph_ptr, n_graphs, dim, n_iters, w_ih, w_hh, save,
+                          g_outa, g_outb, dxa, dxb, n_rows, dgates, dw_ih, dw_hh, db_ih, db_hh,
+                          stream);
 }
 
 extern "C" int scgib_set2set_wgrad(const float *save, const float *dgates, int64_t n_graphs,

@@ -27,6 +27,13 @@ Differences from the reference, all deliberate:
     ``_last_noise`` — under ops.NoisePrefetch the static buffers, which the
     step's backward refills with the next step's draw), or passed explicitly with
     ``noise=(u_gate[N], u_feat[N,64])`` for parity with a recorded run;
+  * ``args.readout_f`` / ``args.useAtt`` take the reference's values in all
+    four classes: anything but "sum" is the Set2Set readout (both contrastive
+    readouts through ops.set2set_pair, the loss at width 128), ``useAtt=0``
+    the interaction without the attention; ``reduce_d`` never enters the
+    graph (the query it would feed cancels in the per-graph softmax) and a
+    Mainmodel_continue around a model of the other readout width is refused
+    when it is built (DESIGN.md §16);
   * ``flatten_batch_subgraphs`` may be ``None``: the ego-nets are then built
     on the device from ``batch_g`` (scgib_egonet_*), replacing the offline
     khop_in_subgraph pass and the per-step dgl.batch of the reference;
@@ -426,6 +433,10 @@ DEVICE_NOISE = True
 # heads (C > 16), the MAE / RMSE / BCE-with-logits losses and MetricWrapper's
 # NaN-masked "ignore-flatten" losses on csrc/task_head.hip
 FUSE_HEAD = True
+# readout_f != "sum": the step's two Set2Set readouts (noisy and plain graph
+# features, one LSTM) as one autograd node and one launch per direction
+# (ops.set2set_pair); off: two ops.set2set calls (tools/readout_bench.py's A/B)
+S2S_PAIR = True
 # two Transformer encoders of width 64 behind the folded entry, each one
 # autograd node with one weight-gradient reduce and a dropout lane of its own
 # (ops.gt_encoder_x); off: the generic two-stream branch
@@ -489,9 +500,19 @@ class _SCGIBCore(nn.Module):
         return (torch.rand(n, device=device, dtype=torch.float32),
                 torch.rand(n, self.hidden_dim, device=device, dtype=torch.float32))
 
-    def _extract(self, enc_owner, batch_g, batch_x, ego, x_subs, noise, encoded=None):
+    def _extract(self, enc_owner, batch_g, batch_x, ego, x_subs, noise, encoded=None,
+                 z1_s2s=None, readouts=True):
         """extract_features of ``enc_owner`` (models.py:702-750); returns the
         reference's 4-tuple plus z1 = sum_nodes(noisy) (computed in-kernel).
+        ``enc_owner.useAtt`` = 0 runs the interaction without the attention;
+        ``enc_owner.readout`` != "sum" (the reference: anything else is
+        Set2Set) replaces both readouts by Set2Set ones [B, 128], z1 through
+        ``z1_s2s`` (a wrapper's own Set2Set, models.py:1184) when given.  The
+        attention's query, reduce_d(s2s(noisy)) there, is constant within a
+        graph and cancels in the softmax as the sum readout does, so the
+        interaction launch is the same and reduce_d stays out of the graph.
+        ``readouts`` False: the caller reads the interaction map only (the
+        fine-tune / domain-adaptation heads), no Set2Set readout is run.
         ``encoded`` = (graph_features, subgraphs_features, sub_readout, t, drawn)
         when the encoders already ran (_encode_forked); t = compressor[0](graph
         features) and drawn = the device noise when the encoder pair's core
@@ -513,24 +534,35 @@ class _SCGIBCore(nn.Module):
         # compressor[0] (models.py:1092) runs fused in front of the interaction
         # its aside work (the compressor-BN running update) is enqueued at
         # the model's join_aside(), after the losses (ops.LATE_FORK)
+        use_att = bool(enc_owner.useAtt)
         with ops.aside_deferred():
             if t is not None:
                 comp = enc_owner.compressor
                 im, z1, z2, kl, kl_mean = ops.interaction(graph_features, t, sub_readout, u_gate,
                                                           u_feat, comp[1], comp[3],
                                                           enc_owner.attn_layer, batch_g,
-                                                          enc_owner.training)
+                                                          enc_owner.training, use_att)
             else:
                 im, z1, z2, kl, kl_mean = ops.interaction_lin(graph_features, sub_readout,
                                                               u_gate, u_feat,
                                                               enc_owner.compressor,
                                                               enc_owner.attn_layer, batch_g,
-                                                              enc_owner.training)
+                                                              enc_owner.training, use_att)
         ops.stamp("interaction_end")
         enc_owner._last_kl_mean = kl_mean
         # the draws when noise was None (replayable via noise=)
         enc_owner._last_noise = (u_gate, u_feat) if noise is None else None
         noisy = im[:, : self.hidden_dim]
+        if enc_owner.readout != "sum" and readouts:
+            # the interaction's own sum readouts are unused (their gradients
+            # reach its backward as NULL)
+            inner, outer = enc_owner.s2s, (z1_s2s if z1_s2s is not None else enc_owner.s2s)
+            if S2S_PAIR and outer is inner:
+                z1, z2 = ops.set2set_pair(noisy, graph_features, batch_g, inner.lstm,
+                                          inner.n_iters)
+            else:  # a wrapper's LSTM for z1, the wrapped model's for z2: two launches
+                z1 = ops.set2set(noisy, batch_g, outer.lstm, outer.n_iters)
+                z2 = ops.set2set(graph_features, batch_g, inner.lstm, inner.n_iters)
         return im, kl, noisy, z2, z1
 
     def _encode_forked(self, enc_owner, batch_g, batch_x, fork=True, draw_noise=False,
@@ -648,8 +680,12 @@ class _SCGIBCore(nn.Module):
             with torch.cuda.stream(side):
                 con = semi_loss(z1, z2, batch_size)
         kl_loss = kl_mean  # == torch.mean(KL_tensor) (models.py:679), computed in-kernel
+        # (Set2Set readouts, [B, 128]: the width-128 contrastive kernels in
+        # launches of their own beside ops.mlp2_recon; the fused launch holds
+        # the width-64 body)
         if side is None and self.recons_type == "adj" and FUSE_RECON and FUSE_CONTRAST \
-                and im.is_cuda and im.shape[1] == 2 * self.hidden_dim == 128:
+                and im.is_cuda and im.shape[1] == 2 * self.hidden_dim == 128 \
+                and z1.shape[1] == self.hidden_dim:
             # models.py:1174 + loss_recon_adj (:1256-1262) + batched_semi_loss
             # (:606-629) in the same launches
             rec, con = ops.mlp2_recon_contrastive(im, mlp, batch_g, z1, z2)
@@ -694,8 +730,6 @@ class Mainmodel(_SCGIBCore):
         self.recons_type = args.recons_type
         self.useAtt = args.useAtt
         self.readout = args.readout_f
-        if self.readout != "sum" or not self.useAtt:
-            raise NotImplementedError("the hot path implements readout_f='sum', useAtt=1")
         self.hidden_dim = hidden_dim
         self.k_transition = k_transition
         self.fc1 = nn.Linear(hidden_dim, 1)
@@ -788,6 +822,14 @@ class Mainmodel_continue(_SCGIBCore):
         self.Encoder1 = _make_encoder(encoder, self.in_dim, hidden_dim, args, num_layers, num_heads)
         self.Encoder2 = _make_encoder(encoder, self.in_dim, hidden_dim, args, num_layers, num_heads)
         self.model = load_checkpoint(cp_filename, args)
+        inner_readout = getattr(self.model, "readout", "sum")
+        if (self.readout == "sum") != (inner_readout == "sum"):
+            # the reference fails in the contrastive loss's torch.mm here: its
+            # z1 comes from this wrapper's readout, its z2 from the wrapped
+            # model's (models.py:1184 / :718), 64 against 128 columns
+            raise ValueError(f"Mainmodel_continue: readout_f={self.readout!r} around a model "
+                             f"built with readout_f={inner_readout!r}: the contrastive loss "
+                             "would compare readouts of 64 and 128 columns")
         for p in self.model.parameters():
             p.requires_grad = True
         self.compressor = nn.Sequential(nn.Linear(hidden_dim, hidden_dim),
@@ -805,6 +847,11 @@ class Mainmodel_continue(_SCGIBCore):
         ops.join_aside()
         return im, kl, noisy, z2
 
+    def _wrapper_s2s(self):
+        """This wrapper's Set2Set for the contrastive z1 (models.py:1184), when
+        the readout is Set2Set; None for the sum readout."""
+        return self.s2s if self.readout != "sum" else None
+
     @ops.aside_guard
     def forward(self, batch_g, batch_x, flatten_batch_subgraphs, batch_logMs, x_subs,
                 current_epoch=None, edge_index=None, k_transition=None, device=None,
@@ -815,7 +862,7 @@ class Mainmodel_continue(_SCGIBCore):
             ego, enc = self._encode_forked(self.model, batch_g, batch_x, FORK_ENCODERS,
                                            noise is None)
             im, _, _, z2, z1 = self.model._extract(self.model, batch_g, None, ego, None, noise,
-                                                   enc)
+                                                   enc, self._wrapper_s2s())
             self.model._last_z1 = z1
         else:
             ego = None
@@ -828,6 +875,9 @@ class Mainmodel_continue(_SCGIBCore):
             im, kl, noisy, z2 = self.model.extract_features(None, batch_g, batch_x,
                                                             flatten_batch_subgraphs, x_subs,
                                                             device, noise)
+            if self.readout != "sum":  # z1 through this wrapper's own Set2Set
+                self.model._last_z1 = ops.set2set(noisy, batch_g, self.s2s.lstm,
+                                                  self.s2s.n_iters)
         kl_loss, con, rec = self._losses(batch_g, im, self.model._last_kl_mean,
                                          self.model._last_z1, z2, self.MLP, batch_size,
                                          batch_logMs, ego)
@@ -864,8 +914,6 @@ class Mainmodel_domainadapt(_SCGIBCore):
         self.transfer_d = nn.Linear(in_dim, self.in_dim, bias=False)
         self.batch_size = getattr(args, "batch_size", 16)
         self.useAtt = args.useAtt
-        if self.readout != "sum" or not self.useAtt:
-            raise NotImplementedError("the hot path implements readout_f='sum', useAtt=1")
         self.embedding_h = nn.Linear(self.in_dim, hidden_dim, bias=False)
         self.hidden_dim = hidden_dim
         self.k_transition = k_transition
@@ -920,7 +968,7 @@ class Mainmodel_domainadapt(_SCGIBCore):
             # (folded into their first layers), ego branch forked
             ego, enc = self._encode_forked(inner, batch_g, batch_x, FORK_ENCODERS,
                                            noise is None)
-            im = inner._extract(inner, batch_g, None, ego, None, noise, enc)[0]
+            im = inner._extract(inner, batch_g, None, ego, None, noise, enc, readouts=False)[0]
         else:
             if flatten_batch_subgraphs is None:
                 flatten_batch_subgraphs, x_subs = self._prepare_ego(batch_g, None, batch_x,
@@ -1018,7 +1066,7 @@ class Mainmodel_finetuning(nn.Module):
             # maths as transfer_d then extract_features (models.py:510-513)
             ego, enc = inner._encode_forked(inner, batch_g, batch_x, FORK_ENCODERS,
                                             noise is None, transfer=self.transfer_d)
-            im = inner._extract(inner, batch_g, None, ego, None, noise, enc)[0]
+            im = inner._extract(inner, batch_g, None, ego, None, noise, enc, readouts=False)[0]
             _drop_graph_refs(inner)
         else:
             if flatten_batch_subgraphs is None:  # ego-nets built on the device

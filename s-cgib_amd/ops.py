@@ -123,6 +123,10 @@ class SlabScope:
     def __init__(self):
         self.jobs, self.keep, self.later = [], [], []
         self.open, self.ok, self.callback, self.stream = True, True, False, None
+        # parameters of the loss-section nodes that asked for this scope, and
+        # those two nodes share: autograd sums such a pair's gradients at once,
+        # before a deferred launch has written them, so they are never deferred
+        self.seen, self.shared = set(), set()
         for other in list(SlabScope._live):
             if other.open:  # two forwards awaiting one backward: defer nothing
                 other.ok = self.ok = False
@@ -137,7 +141,8 @@ class SlabScope:
         AccumulateGrad node is not visible from Python: whoever registers one
         that reads the gradient sets ops.DEFER_LOSS_REDUCE = False; this
         package's GradAllReducer reads .grad only after backward returns.)"""
-        return self.open and self.ok and all(
+        return self.open and self.ok and not any(
+            id(p) in self.shared for p in params if p is not None) and all(
             p is None or (SlabScope._device_ok(p) and p.dtype == torch.float32 and p.is_contiguous() and
                           p.is_leaf and p.grad is None and
                           not getattr(p, "_backward_hooks", None) and
@@ -198,7 +203,12 @@ _SLAB_SCOPE = [None]  # the latest encoder pair's scope (captured by later loss 
 def _slab_scope_for(params):
     """The current scope if a backward may defer its reduce into it."""
     sc = _SLAB_SCOPE[0]  # (autograd Function forwards run with grad mode off)
-    return sc if (sc is not None and DEFER_LOSS_REDUCE) else None
+    if sc is None or not DEFER_LOSS_REDUCE:
+        return None
+    for p in params:
+        if p is not None:
+            (sc.shared if id(p) in sc.seen else sc.seen).add(id(p))
+    return sc
 
 
 @contextlib.contextmanager
@@ -1576,6 +1586,79 @@ def set2set(x, graph, lstm, n_iters):
                           lstm.bias_hh_l0, graph.graph_ptr, int(graph.batch_size), int(n_iters))
 
 
+class _Set2SetPair(torch.autograd.Function):
+    """_Set2Set on two inputs over the same graphs with the same LSTM, one
+    launch per direction (scgib_set2set_fwd2 / _bwd2): save, dgates and the
+    outputs hold input a's range, then input b's."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, w_ih, b_ih, w_hh, b_hh, ptr, nseg, n_iters):
+        ctx.set_materialize_grads(False)
+        xa, xb = _f32(xa, "set2set_pair xa"), _f32(xb, "set2set_pair xb")
+        d = xa.shape[1] if xa.dim() == 2 else -1
+        w_ih, w_hh = _f32(w_ih, "lstm.weight_ih_l0"), _f32(w_hh, "lstm.weight_hh_l0")
+        b_ih, b_hh = _f32(b_ih, "lstm.bias_ih_l0"), _f32(b_hh, "lstm.bias_hh_l0")
+        if not (1 <= d <= 64) or xb.shape != xa.shape or tuple(w_ih.shape) != (4 * d, 2 * d) or \
+                tuple(w_hh.shape) != (4 * d, d) or b_ih.numel() != 4 * d or b_hh.numel() != 4 * d:
+            raise _lib.ScgibError(f"set2set_pair: xa {tuple(xa.shape)}, xb {tuple(xb.shape)} "
+                                  f"(one shape, width <= 64), w_ih {tuple(w_ih.shape)}, w_hh "
+                                  f"{tuple(w_hh.shape)}")
+        ctx.leaves = (w_ih, b_ih, w_hh, b_hh)
+        ctx.scope = _slab_scope_for(ctx.leaves)
+        save = torch.empty(max(int(_lib.query("scgib_set2set_save_floats", 2 * nseg, d, n_iters)),
+                               1), dtype=torch.float32, device=xa.device)
+        out = torch.empty(2, nseg, 2 * d, dtype=torch.float32, device=xa.device)
+        _lib.call("scgib_set2set_fwd2", _p(xa), _p(xb), _p(ptr), nseg, d, n_iters, _p(w_ih),
+                  _p(b_ih), _p(w_hh), _p(b_hh), _p(save), _p(out), _stream())
+        ctx.save_for_backward(xa, xb, w_ih, w_hh, save)
+        ctx.ptr, ctx.nseg, ctx.n_iters = ptr, nseg, n_iters
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, ga, gb):
+        xa, xb, w_ih, w_hh, save = ctx.saved_tensors
+        d = xa.shape[1]
+        if ga is None and gb is None:
+            return (None,) * 9
+        # (an output no loss reads: the kernel reads NULL as zero, no fill launch)
+        ga = None if ga is None else _f32(ga, "set2set_pair.backward")
+        gb = None if gb is None else _f32(gb, "set2set_pair.backward")
+        dxa, dxb = torch.empty_like(xa), torch.empty_like(xb)
+        dgates = torch.empty(max(2 * ctx.nseg * ctx.n_iters * 4 * d, 1), dtype=torch.float32,
+                             device=xa.device)
+        n_ih, n_hh = 4 * d * 2 * d, 4 * d * d
+        wbuf = torch.empty(n_ih + n_hh + 8 * d, dtype=torch.float32, device=xa.device)
+        dw_ih = wbuf[:n_ih].view(4 * d, 2 * d)
+        dw_hh = wbuf[n_ih:n_ih + n_hh].view(4 * d, d)
+        db_ih = wbuf[n_ih + n_hh:n_ih + n_hh + 4 * d]
+        db_hh = wbuf[n_ih + n_hh + 4 * d:]
+        ptrs = (dw_ih.data_ptr(), dw_hh.data_ptr(), db_ih.data_ptr(), db_hh.data_ptr())
+        # the LSTM weight gradients (both inputs' rounds, one pass): deferred
+        # past the encoders' backward as _Set2Set's are (SlabScope)
+        scope = getattr(ctx, "scope", None)
+        defer = scope is not None and scope.usable(ctx.leaves)
+        wg = (None,) * 4 if defer else tuple(ctypes.c_void_p(v) for v in ptrs)
+        _lib.call("scgib_set2set_bwd2", _p(xa), _p(xb), _p(ctx.ptr), ctx.nseg, d, ctx.n_iters,
+                  _p(w_ih), _p(w_hh), _p(save), _p(ga), _p(gb), _p(dxa), _p(dxb), xa.shape[0],
+                  _p(dgates), *wg, _stream())
+        if defer:
+            args = (_p(save), _p(dgates), 2 * ctx.nseg, d, ctx.n_iters,
+                    *(ctypes.c_void_p(v) for v in ptrs))
+            scope.defer(lambda: _lib.call("scgib_set2set_wgrad", *args, _stream()),
+                        save, dgates, wbuf)
+        return dxa, dxb, dw_ih, db_ih, dw_hh, db_hh, None, None, None
+
+
+def set2set_pair(xa, xb, graph, lstm, n_iters):
+    """(set2set(xa, ...), set2set(xb, ...)) with one LSTM over the same graphs
+    as one autograd node and one launch per direction (2 B workgroups); the
+    outputs and the data gradients carry the bits of the two separate calls,
+    the LSTM's gradients are the sum over both inputs' rounds in one pass."""
+    return _Set2SetPair.apply(xa, xb, lstm.weight_ih_l0, lstm.bias_ih_l0, lstm.weight_hh_l0,
+                              lstm.bias_hh_l0, graph.graph_ptr, int(graph.batch_size),
+                              int(n_iters))
+
+
 # ---------------------------------------------------------------------------
 # (f)1: fine-tune prediction head + BCE (models.py:510-523), csrc/head.hip
 # ---------------------------------------------------------------------------
@@ -1761,9 +1844,10 @@ def task_loss(scores, targets, kind, ignore_nan=True, return_count=False):
 # A6-A8: fused core <-> subgraph interaction
 # ---------------------------------------------------------------------------
 def _interaction_forward(ctx, f, t, s, u_gate, u_feat, gamma, beta, w2, b2, w_att, b_att, graph,
-                         bn, training):
+                         bn, training, use_att=True):
     """Launch scgib_interaction_fwd (+ the BN running update); stores on ctx
-    what the backward needs and returns (outputs, tensors to save)."""
+    what the backward needs and returns (outputs, tensors to save).
+    ``use_att`` False: the kernels without the attention (the _v2 entries)."""
     u_gate, u_feat = _f32(u_gate, "interaction"), _f32(u_feat, "interaction")
     n, d = f.shape
     if d != HIDDEN:
@@ -1792,10 +1876,15 @@ def _interaction_forward(ctx, f, t, s, u_gate, u_feat, gamma, beta, w2, b2, w_at
     w_att, b_att = _f32(w_att, "w_att"), _f32(b_att, "b_att")
     rm, rv = bn.running_mean, bn.running_var
     st = _stream()
-    _launch("scgib_interaction_fwd", {"n": n, "B": B}, _p(f), _p(t), _p(s), _p(u_gate), _p(u_feat),
-              _p(graph.graph_ptr), B, n, _p(gamma), _p(beta), _p(rm), _p(rv), float(bn.eps),
-              int(training), _p(w2), _p(b2), _p(w_att), _p(b_att), _p(im), _p(z1), _p(z2),
-              _p(lam), _p(logit), _p(stats), _p(kl), _p(kl_mean), int(pad), st)
+    fwd_args = (_p(f), _p(t), _p(s), _p(u_gate), _p(u_feat),
+                _p(graph.graph_ptr), B, n, _p(gamma), _p(beta), _p(rm), _p(rv), float(bn.eps),
+                int(training), _p(w2), _p(b2), _p(w_att), _p(b_att), _p(im), _p(z1), _p(z2),
+                _p(lam), _p(logit), _p(stats), _p(kl), _p(kl_mean), int(pad))
+    if use_att:
+        _launch("scgib_interaction_fwd", {"n": n, "B": B}, *fwd_args, st)
+    else:
+        _launch("scgib_interaction_fwd_v2", {"n": n, "B": B}, *fwd_args, 0, st)
+    ctx.use_att = bool(use_att)
     if training and bn.track_running_stats:
         nbt = bn.num_batches_tracked
 
@@ -1851,29 +1940,36 @@ def _interaction_backward(ctx, saved, g_im, g_z1, g_z2, g_kl, g_klmean):
     pg = torch.empty(PGRAD_STRIDE, dtype=torch.float32, device=dev)
     scope = getattr(ctx, "scope", None)
     defer = B > 0 and scope is not None and scope.usable(ctx.leaves)
-    _launch("scgib_interaction_bwd", {"n": n, "B": B}, _p(g_im), _p(g_z1), _p(g_z2), _p(g_kl), _p(f), _p(t),
-              _p(s), _p(u_feat), _p(ctx.graph.graph_ptr), B, n, _p(gamma), _p(beta),
-              _p(ctx.rm), _p(ctx.rv), ctx.bn_eps, int(ctx.training), _p(w2), _p(w_att),
-              _p(z1), _p(lam), _p(logit), _p(stats), _p(df), _p(dt), _p(ds), _p(pgrad),
-              _p(g_klmean), int(ctx.pad), None if defer else _p(pg), _stream())
+    bwd_args = (_p(g_im), _p(g_z1), _p(g_z2), _p(g_kl), _p(f), _p(t),
+                _p(s), _p(u_feat), _p(ctx.graph.graph_ptr), B, n, _p(gamma), _p(beta),
+                _p(ctx.rm), _p(ctx.rv), ctx.bn_eps, int(ctx.training), _p(w2), _p(w_att),
+                _p(z1), _p(lam), _p(logit), _p(stats), _p(df), _p(dt), _p(ds), _p(pgrad),
+                _p(g_klmean), int(ctx.pad), None if defer else _p(pg))
+    use_att = getattr(ctx, "use_att", True)
+    if use_att:
+        _launch("scgib_interaction_bwd", {"n": n, "B": B}, *bwd_args, _stream())
+    else:
+        _launch("scgib_interaction_bwd_v2", {"n": n, "B": B}, *bwd_args, 0, _stream())
     if defer:  # the per-graph partials are summed by the encoder pair's backward
         scope.add(pgrad, pg, PGRAD_STRIDE, B)
     grads = (pg[65:129], pg[129:193], pg[0:64].view(1, 64), pg[64:65],
              pg[193:321].view(1, 128), pg[321:322])  # dgamma dbeta dW2 db2 dWatt dbatt
+    if not use_att:  # the attention parameters are outside the graph (the reference: None)
+        grads = grads[:4] + (None, None)
     return df, dt, ds, grads
 
 
 class _Interaction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, f, t, s, u_gate, u_feat, gamma, beta, w2, b2, w_att, b_att, graph, bn,
-                training):
+                training, use_att=True):
         ctx.set_materialize_grads(False)  # outputs no loss reads (fine-tune: z1, z2, KL): no fills
-        ctx.leaves = (gamma, beta, w2, b2, w_att, b_att)
+        ctx.leaves = (gamma, beta, w2, b2, w_att, b_att) if use_att else (gamma, beta, w2, b2)
         ctx.scope = _slab_scope_for(ctx.leaves)
         f = _f32(f, "interaction")
         t, s = _f32(t, "interaction"), _f32(s, "interaction")
         outs, saved = _interaction_forward(ctx, f, t, s, u_gate, u_feat, gamma, beta, w2, b2,
-                                           w_att, b_att, graph, bn, training)
+                                           w_att, b_att, graph, bn, training, use_att)
         ctx.save_for_backward(*saved)
         return outs
 
@@ -1881,7 +1977,7 @@ class _Interaction(torch.autograd.Function):
     def backward(ctx, g_im, g_z1, g_z2, g_kl, g_klmean):
         df, dt, ds, grads = _interaction_backward(ctx, ctx.saved_tensors, g_im, g_z1, g_z2, g_kl,
                                                   g_klmean)
-        return (df, dt, ds, None, None) + grads + (None, None, None)
+        return (df, dt, ds, None, None) + grads + (None, None, None, None)
 
 
 class _InteractionLin(torch.autograd.Function):
@@ -1891,7 +1987,7 @@ class _InteractionLin(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, f, w0, b0, s, u_gate, u_feat, gamma, beta, w2, b2, w_att, b_att, graph, bn,
-                training):
+                training, use_att=True):
         ctx.set_materialize_grads(False)  # outputs no loss reads (fine-tune: z1, z2, KL): no fills
         f = _f32(f, "interaction")
         s = _f32(s, "interaction")
@@ -1902,7 +1998,7 @@ class _InteractionLin(torch.autograd.Function):
         _lib.call("scgib_linear_fwd", _p(f), f.shape[0], _p(w0), _p(b0), _p(t), _p(graph.dims),
                   _stream())
         outs, saved = _interaction_forward(ctx, f, t, s, u_gate, u_feat, gamma, beta, w2, b2,
-                                           w_att, b_att, graph, bn, training)
+                                           w_att, b_att, graph, bn, training, use_att)
         ctx.save_for_backward(*saved, w0)
         return outs
 
@@ -1921,10 +2017,10 @@ class _InteractionLin(torch.autograd.Function):
         _lib.call("scgib_linear_bwd", _p(dt), _p(f), _p(w0), n, _p(df), _p(df_total), _p(slab),
                   _p(wg), _p(ctx.graph.dims), _stream())
         dw0, db0 = wg[: HIDDEN * HIDDEN].view(HIDDEN, HIDDEN), wg[HIDDEN * HIDDEN:]
-        return (df_total, dw0, db0, ds, None, None) + grads + (None, None, None)
+        return (df_total, dw0, db0, ds, None, None) + grads + (None, None, None, None)
 
 
-def interaction(f, t, s, u_gate, u_feat, bn, lin2, attn, graph, training):
+def interaction(f, t, s, u_gate, u_feat, bn, lin2, attn, graph, training, use_att=True):
     """Fused compression + attention (models.py:595-660, 714-749).
 
     ``bn`` is the compressor BatchNorm1d (its running stats are updated in
@@ -1933,19 +2029,22 @@ def interaction(f, t, s, u_gate, u_feat, bn, lin2, attn, graph, training):
     Returns (interaction_map [N,128], z1 = sum_nodes(noisy) [B,64],
     z2 = sum_nodes(f) [B,64], kl_tensor [2 n_last, 64] (empty in capacity
     mode), kl_mean = mean(kl_tensor) [scalar]).
+    ``use_att`` False (the reference's useAtt = 0): interaction_map[:, 64:] is
+    ``s`` itself and ``attn``'s parameters get no gradient (None).
     """
     return _Interaction.apply(f, t, s, u_gate, u_feat, bn.weight, bn.bias, lin2.weight,
-                              lin2.bias, attn.weight, attn.bias, graph, bn, bool(training))
+                              lin2.bias, attn.weight, attn.bias, graph, bn, bool(training),
+                              bool(use_att))
 
 
-def interaction_lin(f, s, u_gate, u_feat, compressor, attn, graph, training):
+def interaction_lin(f, s, u_gate, u_feat, compressor, attn, graph, training, use_att=True):
     """interaction() with t = compressor[0](f) computed by the fused dense
     kernels (the model's path): ``compressor`` is the Sequential(Linear,
     BatchNorm1d, ReLU, Linear) of models.py:589-592."""
     lin0, bn, lin2 = compressor[0], compressor[1], compressor[3]
     return _InteractionLin.apply(f, lin0.weight, lin0.bias, s, u_gate, u_feat, bn.weight, bn.bias,
                                  lin2.weight, lin2.bias, attn.weight, attn.bias, graph, bn,
-                                 bool(training))
+                                 bool(training), bool(use_att))
 
 
 # ---------------------------------------------------------------------------
@@ -2153,21 +2252,31 @@ class NoisePrefetch:
 # ---------------------------------------------------------------------------
 # A11: contrastive loss (batched_semi_loss, tau = 1)
 # ---------------------------------------------------------------------------
+CONTRAST_WIDTHS = (64, 128)  # sum readouts | Set2Set readouts (csrc/contrast_body.h)
+
+
 class _Contrastive(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z1, z2):
         z1 = _f32(z1, "contrastive z1")
         z2 = _f32(z2, "contrastive z2")
         B = z1.shape[0]
-        if z1.shape != (B, HIDDEN) or z2.shape != (B, HIDDEN):
+        width = z1.shape[1] if z1.dim() == 2 else -1
+        if width not in CONTRAST_WIDTHS or z1.shape != (B, width) or z2.shape != (B, width):
             raise _lib.ScgibError(f"contrastive: z1 {tuple(z1.shape)} / z2 {tuple(z2.shape)} "
-                                  f"must both be [B, {HIDDEN}]")
-        ws = torch.empty(int(_lib.query("scgib_contrastive_workspace_floats", B)),
-                         dtype=torch.float32, device=z1.device)
+                                  f"must both be [B, 64] or both [B, 128]")
         loss = torch.empty((), dtype=torch.float32, device=z1.device)
         cnt = counters(z1.device, "contrastive", int(_lib.query("scgib_contrastive_counters", B)))
-        _lib.call("scgib_contrastive_fwd", _p(z1), _p(z2), B, _p(ws), _p(loss), _p(cnt),
-                  _stream())
+        if width == HIDDEN:
+            ws = torch.empty(int(_lib.query("scgib_contrastive_workspace_floats", B)),
+                             dtype=torch.float32, device=z1.device)
+            _lib.call("scgib_contrastive_fwd", _p(z1), _p(z2), B, _p(ws), _p(loss), _p(cnt),
+                      _stream())
+        else:
+            ws = torch.empty(int(_lib.query("scgib_contrastive_workspace_floats_w", B, width)),
+                             dtype=torch.float32, device=z1.device)
+            _lib.call("scgib_contrastive_fwd_w", _p(z1), _p(z2), B, width, _p(ws), _p(loss),
+                      _p(cnt), _stream())
         ctx.save_for_backward(z1, z2, ws)
         return loss
 
@@ -2178,14 +2287,23 @@ class _Contrastive(torch.autograd.Function):
         g = _f32(g, "contrastive.backward").reshape(1)
         dz1, dz2 = torch.empty_like(z1), torch.empty_like(z2)
         cnt = counters(z1.device, "contrastive", int(_lib.query("scgib_contrastive_counters", B)))
-        _lib.call("scgib_contrastive_bwd", _p(z1), _p(z2), B, _p(ws), _p(g), _p(dz1), _p(dz2),
-                  _p(cnt), _stream())
+        if z1.shape[1] == HIDDEN:
+            _lib.call("scgib_contrastive_bwd", _p(z1), _p(z2), B, _p(ws), _p(g), _p(dz1),
+                      _p(dz2), _p(cnt), _stream())
+        else:
+            _lib.call("scgib_contrastive_bwd_w", _p(z1), _p(z2), B, z1.shape[1], _p(ws), _p(g),
+                      _p(dz1), _p(dz2), _p(cnt), _stream())
         return dz1, dz2
 
 
 def contrastive(z1, z2):
     """batched_semi_loss(z1, z2, chunk) with tau = 1 (models.py:606-629); the
-    value does not depend on the chunk size."""
+    value does not depend on the chunk size.  Rows of width 64 (the sum
+    readouts) or 128 (the Set2Set readouts); any other width is refused."""
+    if z1.dim() != 2 or z2.dim() != 2 or z1.shape[1] not in CONTRAST_WIDTHS or \
+            z1.shape != z2.shape:
+        raise _lib.ScgibError(f"contrastive: z1 {tuple(z1.shape)} / z2 {tuple(z2.shape)} "
+                              f"must both be [B, 64] or both [B, 128]")
     return _Contrastive.apply(z1, z2)
 
 
