@@ -2970,7 +2970,13 @@ def gt_layer(h, graph, layer, drop_mask=None, return_aux=False):
 def gt_encoder(h, graph, module, drop_masks=None):
     """A whole models.Transformer forward: embedding_h (one torch F.linear,
     [N, in_dim] x [in_dim, 64]) and then every layer through gt_layer's own
-    autograd op.  ``drop_masks``: one mask per layer (see gt_layer)."""
+    autograd op.  ``drop_masks``: one mask per layer (see gt_layer).
+
+    On a padded StaticBatch the layers' results are bitwise those of the
+    unpadded batch; the F.linear's own two gradients (dh, embedding_h.weight)
+    are so only while the BLAS library picks one GEMM kernel for both row
+    counts.  gt_encoder_x, the model step's entry, folds the
+    embedding into a kernel with a fixed summation order."""
     if not h.is_cuda:
         raise _lib.ScgibError(f"gt_encoder: tensor is on {h.device}; the S-CGIB ops run on the "
                               "HIP device only (no CPU fallback)")

@@ -20,6 +20,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import big_graphs as BG
 from conftest import check_grads_model, rel_err, rel_l2
 from oracle import egonet
 from oracle import scgib_ref as R
@@ -135,6 +136,12 @@ def _path(n):
     return np.concatenate([a, a + 1]), np.concatenate([a + 1, a]), n
 
 
+def _star(k):
+    leaves = np.arange(1, k + 1)
+    zeros = np.zeros(k, np.int64)
+    return np.concatenate([leaves, zeros]), np.concatenate([zeros, leaves]), k + 1
+
+
 def _hand_graphs():
     out = {"single": (np.zeros(0, np.int64), np.zeros(0, np.int64), 1)}
     out["path64"] = _path(64)
@@ -143,18 +150,10 @@ def _hand_graphs():
     s, d, _ = _path(4)
     out["isolated_first"] = (s + 1, d + 1, 5)
     # star: 9 leaves <-> centre 0 (in-degree 9: gather rounds of 4 at 5 and 9)
-    leaves = np.arange(1, 10)
-    out["star9"] = (np.concatenate([leaves, np.zeros(9, np.int64)]),
-                    np.concatenate([np.zeros(9, np.int64), leaves]), 10)
-    # directed, non-symmetric: v -> v+1, v -> v+3, v -> 2v (mod n), no reverse edges kept
-    n = 70
-    edges = set()
-    for v in range(n):
-        for u in ((v + 1) % n, (v + 3) % n, (2 * v + 5) % n):
-            if u != v and (u, v) not in edges:
-                edges.add((v, u))
-    e = np.array(sorted(edges), np.int64)
-    out["directed"] = (e[:, 0], e[:, 1], n)
+    out["star9"] = _star(9)
+    out["star33"] = _star(33)  # in-degree 33: nine gather rounds, the last one of a single edge
+    # directed, non-symmetric: v -> v+1, v -> v+3, v -> 2v+5 (mod n), no reverse edges kept
+    out["directed"] = BG.directed(70)
     return out
 
 
@@ -185,9 +184,40 @@ def test_layer_hand_made_graphs(pkg, dev, name, mode):
         assert rel_err(out[0].cpu(), want) < ACT_TOL
 
 
-@pytest.mark.parametrize("mode,shape", [("gcn", (128, 128)), ("mean", (64, 64))])
-def test_layer_deterministic(pkg, dev, mols37, mode, shape):
-    g = mols37.to(dev)
+@pytest.fixture(scope="module")
+def big(pkg):
+    """name -> host graph of BG.big_directed(name), built once for the module."""
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            src, dst, n = BG.big_directed(name)
+            gh = pkg.graph.GraphBatch.from_edges(src, dst, n, symmetric_hint=False)
+            assert BG.degree_asymmetry(src, dst, n) > 0.5  # a backward over the wrong CSR cannot pass
+            es, ed = gh.edges()  # the reference's edge list is the input's
+            assert sorted(zip(es.tolist(), ed.tolist())) == sorted(zip(src.tolist(), dst.tolist()))
+            cache[name] = gh
+        return cache[name]
+    return get
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name", list(BG.BIG_SIZES))
+def test_layer_past_256_tiles(pkg, dev, big, name, mode, shape):
+    """conv_wgrad_k runs at most 256 workgroups.  big256: one full tile each,
+    the boundary; big257: 258 tiles, workgroups 0 and 1 walk a second tile and
+    the last one holds 6 rows.  A third of the edges leave their tile's
+    neighbourhood, so the dx gather reads dz rows that other workgroups wrote."""
+    gh = big(name)
+    n = gh.num_nodes()
+    assert pkg._lib.query("scgib_conv_slabs", n) == BG.GRID_CAP
+    assert BG.tiles(n) == (BG.GRID_CAP if name == "big256" else BG.GRID_CAP + 2)
+    check_layer(pkg, dev, gh, mode, shape[0], shape[1], True, seed=shape[0] + shape[1])
+
+
+def _layer_twice(pkg, dev, gh, mode, shape):
+    g = gh.to(dev)
     n = g.num_nodes()
     gen = torch.Generator().manual_seed(1)
     x = torch.randn(n, shape[0], generator=gen)
@@ -200,6 +230,16 @@ def test_layer_deterministic(pkg, dev, mols37, mode, shape):
         assert (ga is None) == (gc is None)
         if ga is not None:
             assert torch.equal(ga, gc)
+
+
+@pytest.mark.parametrize("mode,shape", [("gcn", (128, 128)), ("mean", (64, 64))])
+def test_layer_deterministic(pkg, dev, mols37, mode, shape):
+    _layer_twice(pkg, dev, mols37, mode, shape)
+
+
+@pytest.mark.parametrize("mode,shape", [("gcn", (128, 128)), ("mean", (64, 64))])
+def test_layer_deterministic_past_256_tiles(pkg, dev, big, mode, shape):
+    _layer_twice(pkg, dev, big("big257"), mode, shape)
 
 
 def test_unsupported_shapes_are_refused(pkg, dev, mols37):
@@ -266,9 +306,7 @@ def hip_relu_masks(pkg, enc, g, h):
     return masks, h
 
 
-@pytest.mark.parametrize("name", ["GCN", "GraphSAGE"])
-def test_encoder_matches_fp64(pkg, dev, name):
-    gh, _ = pkg.graph.collate_pyg(pkg.synth.molecules(40, "qm9", seed=9))
+def check_encoder(pkg, dev, name, gh):
     g = gh.to(dev)
     n = gh.num_nodes()
     src, dst = gh.edges()
@@ -309,6 +347,23 @@ def test_encoder_matches_fp64(pkg, dev, name):
             assert rel_l2(got, first) > 1e-2 and rel_l2(got, second) > 1e-2, key
 
 
+@pytest.mark.parametrize("name", ["GCN", "GraphSAGE"])
+def test_encoder_matches_fp64(pkg, dev, name):
+    gh, _ = pkg.graph.collate_pyg(pkg.synth.molecules(40, "qm9", seed=9))
+    check_encoder(pkg, dev, name, gh)
+
+
+@pytest.mark.parametrize("name", ["GCN", "GraphSAGE"])
+def test_encoder_matches_fp64_past_256_tiles(pkg, dev, name):
+    """258 tiles, the last of 30 rows: the inter-layer mask fusion, the
+    256-slab reduce and "encoder == chained public op" at that size."""
+    gh = BG.big_molecules(pkg)
+    n = gh.num_nodes()
+    assert n > 256 * 64 and n % 64 != 0
+    assert pkg._lib.query("scgib_conv_slabs", n) == BG.GRID_CAP
+    check_encoder(pkg, dev, name, gh)
+
+
 def _encoder_step(enc, g, h, gout):
     for p in enc.parameters():
         p.grad = None
@@ -318,14 +373,13 @@ def _encoder_step(enc, g, h, gout):
     return out
 
 
-@pytest.mark.parametrize("name", ["GCN", "GraphSAGE"])
-def test_encoder_capacity_mode(pkg, dev, name):
+def check_capacity_mode(pkg, dev, name, gh, capacities, oracle):
     """A StaticBatch with spare rows: live rows bitwise the unpadded run's,
-    padded rows of out / dx zero, weight gradients bitwise equal."""
-    B = 48
-    gh, _ = pkg.graph.collate_pyg(pkg.synth.molecules(B, "qm9", seed=21))
+    padded rows of out / dx zero, weight gradients bitwise equal.  ``oracle``:
+    the capacity run's gradients against fp64 as well."""
+    B = gh.batch_size
     n = gh.num_nodes()
-    n_cap, e_cap, mgn, caps = pkg.graph.StaticBatch.capacities([gh], 1, slack=1.3)
+    n_cap, e_cap, mgn, caps = capacities
     assert (n_cap + 63) // 64 > (n + 63) // 64  # whole spare tiles, and a partly live one
     static = pkg.graph.StaticBatch(B, n_cap, e_cap, gh.ndata["x"].shape[1], mgn, caps, dev)
     static.load(static.pad(gh))
@@ -349,6 +403,20 @@ def test_encoder_capacity_mode(pkg, dev, name):
         if k in grads:
             assert torch.equal(p.grad, grads[k]), k
 
+    if oracle:  # not only a self-comparison: the capacity run against fp64
+        masks, _ = hip_relu_masks(pkg, enc, g, h.detach())
+        src, dst = gh.edges()
+        pr = {k: v.detach().cpu().double().requires_grad_(True) for k, v in enc.state_dict().items()}
+        hr = h_cap[:n].cpu().double().requires_grad_(True)
+        ref = ref_encoder(pr, "", name, src, dst, hr, masks)
+        ref.backward(go_cap[:n].cpu().double())
+        assert rel_err(out_c[:n].detach().cpu(), ref.detach()) < ACT_TOL
+        assert rel_l2(hc.grad[:n].cpu(), hr.grad) < GRAD_TOL
+        for k, p in enc.named_parameters():
+            if k in grads:
+                err = rel_l2(p.grad.cpu(), pr[k].grad)
+                assert err < GRAD_TOL, (k, err)
+
     # the public layer op with its own ReLU mask (dz materialised) likewise
     _, mode = layer_plan(name)
     wn, ws, b = enc.conv2.conv_params()
@@ -368,6 +436,25 @@ def test_encoder_capacity_mode(pkg, dev, name):
     assert torch.equal(o_c[:n], o_e) and torch.count_nonzero(o_c[n:]) == 0
     assert torch.equal(g_c[0][:n], g_e[0]) and torch.count_nonzero(g_c[0][n:]) == 0
     assert torch.equal(g_c[1], g_e[1]) and torch.equal(g_c[2], g_e[2])
+
+
+@pytest.mark.parametrize("name", ["GCN", "GraphSAGE"])
+def test_encoder_capacity_mode(pkg, dev, name):
+    gh, _ = pkg.graph.collate_pyg(pkg.synth.molecules(48, "qm9", seed=21))
+    check_capacity_mode(pkg, dev, name, gh, pkg.graph.StaticBatch.capacities([gh], 1, slack=1.3),
+                        False)
+
+
+@pytest.mark.parametrize("split", list(BG.CAPACITY_SPLITS))
+@pytest.mark.parametrize("name", ["GCN", "GraphSAGE"])
+def test_encoder_capacity_mode_across_256_tiles(pkg, dev, name, split):
+    """The same assertions with the 256-workgroup line between or behind the
+    live tiles (BG.CAPACITY_SPLITS): a workgroup's second tile live, partly
+    live or padded, and workgroups that meet padding only.  Tile -> workgroup
+    is tile mod 256 in both runs and trailing zero slabs add +0.0 to their
+    partition, so the bitwise claim carries over."""
+    gh, capacities = BG.capacity_case(pkg, split)
+    check_capacity_mode(pkg, dev, name, gh, capacities, True)
 
 
 @pytest.mark.parametrize("name", ["GCN", "GraphSAGE"])

@@ -22,6 +22,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import big_graphs as BG
 from conftest import CANCELLED, check_grads_model, rel_err, rel_l2
 from oracle import egonet
 from oracle import scgib_ref as R
@@ -64,14 +65,8 @@ def _hand_graphs():
     out["isolated_first"] = (s + 1, d + 1, 5)
     out["star9"] = _star(9)
     out["star33"] = _star(33)  # in-degree 33: beyond any small unroll
-    n = 70  # directed, non-symmetric: v -> v+1, v -> v+3, v -> 2v+5 (mod n), no reverse edges kept
-    edges = set()
-    for v in range(n):
-        for u in ((v + 1) % n, (v + 3) % n, (2 * v + 5) % n):
-            if u != v and (u, v) not in edges:
-                edges.add((v, u))
-    e = np.array(sorted(edges), np.int64)
-    out["directed"] = (e[:, 0], e[:, 1], n)
+    # directed, non-symmetric: v -> v+1, v -> v+3, v -> 2v+5 (mod n), no reverse edges kept
+    out["directed"] = BG.directed(70)
     return out
 
 
@@ -79,7 +74,9 @@ HAND = _hand_graphs()
 
 
 class Case:
-    """A host graph, its device copy and the edge list the fp64 side sums over."""
+    """A host graph, its device copy and the edge list the fp64 side sums over.
+    ``name``: "mols", a hand graph, or a BG.BIG_SIZES graph (the directed
+    recipe just past 256 tiles)."""
 
     def __init__(self, pkg, dev, name):
         if name == "mols":
@@ -87,9 +84,9 @@ class Case:
             assert self.gh.num_nodes() % 64 != 0 and self.gh.num_nodes() > 3 * 64
             self.src, self.dst = self.gh.edges()
         else:
-            src, dst, n = HAND[name]
+            src, dst, n = BG.big_directed(name) if name in BG.BIG_SIZES else HAND[name]
             self.gh = pkg.graph.GraphBatch.from_edges(src, dst, n, symmetric_hint=False)
-            if name == "directed":
+            if name == "directed" or name in BG.BIG_SIZES:
                 din, dout = np.bincount(dst, minlength=n), np.bincount(src, minlength=n)
                 assert (din != dout).mean() > 0.5  # a backward over the wrong CSR cannot pass
             # the reference's edge list is the input's, not read back from the CSR under test
@@ -224,10 +221,7 @@ def ref_attention_grads(inputs, c, heads, score, clamp=True):
     return attn.detach(), e.detach(), [t.grad for t in leaves]
 
 
-@pytest.mark.parametrize("heads", HEADS)
-@pytest.mark.parametrize("name", ["mols"] + list(HAND))
-def test_attention_op(pkg, case, name, heads):
-    c = case(name)
+def check_attention_op(pkg, c, heads):
     inputs, attn, score, grads = run_attention(pkg, c, heads, 1.0, 11 + heads)
     sc = score[c.score_row].cpu()
     ref, e, rgrads = ref_attention_grads(inputs, c, heads, sc)
@@ -240,6 +234,21 @@ def test_attention_op(pkg, case, name, heads):
     for v in torch.nonzero(indeg == 0).flatten().tolist():  # isolated: exact zeros
         assert torch.count_nonzero(attn[v]) == 0
         assert torch.count_nonzero(grads[0][v]) == 0
+
+
+@pytest.mark.parametrize("heads", HEADS)
+@pytest.mark.parametrize("name", ["mols"] + list(HAND))
+def test_attention_op(pkg, case, name, heads):
+    check_attention_op(pkg, case(name), heads)
+
+
+@pytest.mark.parametrize("heads", HEADS)
+def test_attention_op_past_256_tiles(pkg, case, heads):
+    """16,454 rows: the 2v+5 edges make both backward walks (by destination,
+    then by source over the transposed CSR) read rows of far workgroups."""
+    c = case("big257")
+    assert BG.tiles(c.n) > BG.GRID_CAP and c.n % BG.TILE == 6
+    check_attention_op(pkg, c, heads)
 
 
 @pytest.mark.parametrize("heads", HEADS)
@@ -311,10 +320,7 @@ def layer_mode(pkg, c, mode, seed):
     return layer, mask, 4242 if mode == "drawn" else None
 
 
-@pytest.mark.parametrize("mode", ["eval", "mask", "drawn"])
-@pytest.mark.parametrize("name", ["mols", "directed"])
-def test_layer_matches_fp64(pkg, case, name, mode):
-    c = case(name)
+def check_layer_fp64(pkg, c, mode):
     layer, mask, seed = layer_mode(pkg, c, mode, 5)
     h0, gout = layer_inputs(c, 31)
     out, aux, dh, grads = run_layer(pkg, c, layer, h0, gout, mask, seed)
@@ -336,8 +342,25 @@ def test_layer_matches_fp64(pkg, case, name, mode):
 
 
 @pytest.mark.parametrize("mode", ["eval", "mask", "drawn"])
-def test_layer_deterministic(pkg, case, mode):
-    c = case("mols")
+@pytest.mark.parametrize("name", ["mols", "directed"])
+def test_layer_matches_fp64(pkg, case, name, mode):
+    check_layer_fp64(pkg, case(name), mode)
+
+
+@pytest.mark.parametrize("mode", ["eval", "mask"])
+@pytest.mark.parametrize("name", list(BG.BIG_SIZES))
+def test_layer_past_256_tiles(pkg, case, name, mode):
+    """gt_lin_bwd_k runs at most 256 workgroups.  big256: one full tile each,
+    the boundary; big257: 258 tiles, workgroups 0 and 1 walk a second tile
+    (weight, bias and LayerNorm accumulators live across it) and the last one
+    holds 6 rows."""
+    c = case(name)
+    assert pkg._lib.query("scgib_gt_slabs", c.n) == BG.GRID_CAP
+    assert BG.tiles(c.n) == (BG.GRID_CAP if name == "big256" else BG.GRID_CAP + 2)
+    check_layer_fp64(pkg, c, mode)
+
+
+def _layer_twice(pkg, c, mode):
     layer, mask, seed = layer_mode(pkg, c, mode, 6)
     h0, gout = layer_inputs(c, 32)
     a = run_layer(pkg, c, layer, h0, gout, mask, seed)
@@ -347,6 +370,15 @@ def test_layer_deterministic(pkg, case, mode):
     assert set(a[3]) == set(b[3])
     for k in a[3]:
         assert torch.equal(a[3][k], b[3][k]), k
+
+
+@pytest.mark.parametrize("mode", ["eval", "mask", "drawn"])
+def test_layer_deterministic(pkg, case, mode):
+    _layer_twice(pkg, case("mols"), mode)
+
+
+def test_layer_deterministic_past_256_tiles(pkg, case):
+    _layer_twice(pkg, case("big257"), "drawn")
 
 
 # ---------------------------------------------------------------------------
@@ -378,8 +410,17 @@ class EdgeList:
         self.src, self.dst = src, dst
 
 
-def test_encoder_matches_fp64(pkg, dev):
-    gh, _ = pkg.graph.collate_pyg(pkg.synth.molecules(40, "qm9", seed=9))
+def score_rows(gh, c):
+    """Row of the kernels' [E, heads] score (dst-major CSR order) of each edge of c."""
+    n = gh.num_nodes()
+    rp, col = gh.rowptr.long(), gh.col.long()
+    cdst = torch.repeat_interleave(torch.arange(n), rp[1:] - rp[:-1])
+    key = cdst * n + col
+    order = torch.argsort(key)
+    return order[torch.searchsorted(key[order], c.dst * n + c.src)]
+
+
+def check_encoder_fp64(pkg, dev, gh):
     g, n = gh.to(dev), gh.num_nodes()
     enc = make_encoder(pkg, dev, 1).train()
     assert len(enc.layers) == 5
@@ -402,11 +443,7 @@ def test_encoder_matches_fp64(pkg, dev):
     assert torch.equal(x, out.detach())
 
     c = EdgeList(*gh.edges())
-    rp, col = gh.rowptr.long(), gh.col.long()
-    cdst = torch.repeat_interleave(torch.arange(n), rp[1:] - rp[:-1])
-    key = cdst * n + col
-    order = torch.argsort(key)
-    c.score_row = order[torch.searchsorted(key[order], c.dst * n + c.src)]
+    c.score_row = score_rows(gh, c)
     p = ref_params(enc)
     hr = h0.double().requires_grad_(True)
     ref = ref_encoder(p, "", c, hr, 5, 4, True, [m.cpu() for m in masks], auxes)
@@ -423,6 +460,22 @@ def test_encoder_matches_fp64(pkg, dev):
             check_grad(k, mine[k].grad, r.grad, p[k.rsplit(".", 1)[0] + ".weight"].grad)
     for k, v in enc.named_buffers():  # the BatchNorm statistics never move
         assert torch.equal(v, buffers[k]), k
+
+
+def test_encoder_matches_fp64(pkg, dev):
+    gh, _ = pkg.graph.collate_pyg(pkg.synth.molecules(40, "qm9", seed=9))
+    check_encoder_fp64(pkg, dev, gh)
+
+
+def test_encoder_matches_fp64_past_256_tiles(pkg, dev):
+    """258 tiles, the last of 30 rows: five layers, each with its three
+    backward tile kernels and the 256-slab reduce, and "encoder == chained
+    public op" at that size."""
+    gh = BG.big_molecules(pkg)
+    n = gh.num_nodes()
+    assert n > 256 * 64 and n % 64 != 0
+    assert pkg._lib.query("scgib_gt_slabs", n) == BG.GRID_CAP
+    check_encoder_fp64(pkg, dev, gh)
 
 
 def test_module_forwards(pkg, case, dev):
@@ -494,13 +547,15 @@ def _encoder_step(pkg, enc, g, h, gout, seed):
     return out
 
 
-def test_encoder_capacity_mode(pkg, dev):
+def check_capacity_mode(pkg, dev, gh, capacities, oracle, torch_gemm_bitwise=True):
     """A StaticBatch with spare rows: live rows bitwise the unpadded run's,
-    padded rows of out / dx zero, weight gradients bitwise equal."""
-    B = 48
-    gh, _ = pkg.graph.collate_pyg(pkg.synth.molecules(B, "qm9", seed=21))
+    padded rows of out / dx zero, weight gradients bitwise equal.  ``oracle``:
+    the capacity run's gradients against fp64 as well.  ``torch_gemm_bitwise``
+    off: the two results of torch's own GEMM (see below) within a reordered
+    fp32 sum instead, and dh0 at the layer stack's input bitwise."""
+    B = gh.batch_size
     n = gh.num_nodes()
-    n_cap, e_cap, mgn, caps = pkg.graph.StaticBatch.capacities([gh], 1, slack=1.3)
+    n_cap, e_cap, mgn, caps = capacities
     assert (n_cap + 63) // 64 > (n + 63) // 64  # whole spare tiles, and a partly live one
     static = pkg.graph.StaticBatch(B, n_cap, e_cap, gh.ndata["x"].shape[1], mgn, caps, dev)
     static.load(static.pad(gh))
@@ -519,13 +574,89 @@ def test_encoder_capacity_mode(pkg, dev):
     hc = h_cap.clone().requires_grad_(True)
     out_c = _encoder_step(pkg, enc, static.graph, hc, go_cap, 77)
     torch.cuda.synchronize()
-    assert torch.equal(out_c[:n], out) and torch.equal(hc.grad[:n], dx)
+    assert torch.equal(out_c[:n], out)
     assert torch.count_nonzero(out_c[n:]) == 0 and torch.count_nonzero(hc.grad[n:]) == 0
+    differ = {}
+    if not torch.equal(hc.grad[:n], dx):
+        differ["dx"] = rel_l2(hc.grad[:n].cpu(), dx.cpu())
     for k, p in enc.named_parameters():
-        if k in grads:
-            assert torch.equal(p.grad, grads[k]), k
-        else:
+        if k not in grads:
             assert p.grad is None, k
+        elif not torch.equal(p.grad, grads[k]):
+            differ[k] = rel_l2(p.grad.cpu(), grads[k].cpu())
+    print(f"n {n} n_cap {n_cap}: not bitwise {differ}")
+    if torch_gemm_bitwise:
+        assert not differ, differ
+    else:
+        # ops.gt_encoder's embedding_h is one torch F.linear, forward and
+        # backward: dx = dh0 We sums 64 terms and dWe = dh0^T h sums one term
+        # per row, in the order of the GEMM kernel that the BLAS library picks
+        # for n rows, resp. n_cap.  Two fp32 sums of the same K terms in
+        # different orders stay within about sqrt(K) 2^-24 of each other
+        # (padded rows add exact zeros); twice that is the bar.  Every
+        # gradient the project's own kernels write stays bitwise, and so does
+        # dh0, which the layer stack run from a leaf h0 shows below.
+        terms = {"dx": 64, "embedding_h.weight": n}
+        assert set(differ) <= set(terms), differ
+        for k, err in differ.items():
+            assert err < 2 * terms[k] ** 0.5 * 2.0 ** -24, (k, err)
+        res = []
+        with torch.no_grad():
+            h0_live = F.linear(h_cap[:n], enc.embedding_h.weight)
+        for graph, rows in ((g, n), (static.graph, n_cap)):
+            h0 = torch.cat([h0_live, go_cap[n:rows]]).requires_grad_(True)  # live-looking padding
+            pkg.ops.seed_dropout(dev, 77)
+            x = h0
+            for layer in enc.layers:
+                x = pkg.ops.gt_layer(x, graph, layer)
+            (dh0,) = torch.autograd.grad(x, h0, go_cap[:rows].contiguous())
+            res.append((x.detach(), dh0))
+        torch.cuda.synchronize()
+        (x_e, dh0_e), (x_c, dh0_c) = res
+        assert torch.equal(x_e, out) and torch.equal(x_c[:n], out)
+        assert torch.equal(dh0_c[:n], dh0_e) and torch.count_nonzero(dh0_c[n:]) == 0
+        assert float(dh0_e.abs().max()) > 0
+
+    if oracle:  # not only a self-comparison: the capacity run against fp64
+        auxes = []
+        pkg.ops.seed_dropout(dev, 77)  # the masks both runs drew, from the chained public op
+        with torch.no_grad():
+            x = F.linear(h.detach(), enc.embedding_h.weight)
+            for layer in enc.layers:
+                x, aux = pkg.ops.gt_layer(x, g, layer, return_aux=True)
+                auxes.append(aux)
+        assert torch.equal(x, out.detach())
+        c = EdgeList(*gh.edges())
+        c.score_row = score_rows(gh, c)
+        pr = ref_params(enc)
+        hr = h_cap[:n].cpu().double().requires_grad_(True)
+        ref = ref_encoder(pr, "", c, hr, 5, 4, True, [a["keep"].cpu() for a in auxes], auxes)
+        ref.backward(go_cap[:n].cpu().double())
+        assert rel_err(out_c[:n].detach().cpu(), ref.detach()) < ACT_TOL
+        check_grad("dh", hc.grad[:n], hr.grad)
+        for k, p in enc.named_parameters():
+            if k in grads:
+                check_grad(k, p.grad, pr[k].grad, pr[k.rsplit(".", 1)[0] + ".weight"].grad)
+
+
+def test_encoder_capacity_mode(pkg, dev):
+    gh, _ = pkg.graph.collate_pyg(pkg.synth.molecules(48, "qm9", seed=21))
+    check_capacity_mode(pkg, dev, gh, pkg.graph.StaticBatch.capacities([gh], 1, slack=1.3), False)
+
+
+@pytest.mark.parametrize("split", list(BG.CAPACITY_SPLITS))
+def test_encoder_capacity_mode_across_256_tiles(pkg, dev, split):
+    """The same assertions with the 256-workgroup line between or behind the
+    live tiles (BG.CAPACITY_SPLITS): a workgroup's second tile live, partly
+    live or padded, and workgroups that meet padding only.  Tile -> workgroup
+    is tile mod 256 in both runs and trailing zero slabs add +0.0 to their
+    partition, so the bitwise claim carries over for all 80 gradients of the
+    layers' kernels and for dh0.  It does not for the torch F.linear in front
+    of them (measured on its first run: embedding_h.weight 2.1e-6 apart at
+    16,613 live / 17,112 capacity rows): at these row counts the BLAS library
+    picks another kernel for n_cap rows than for n."""
+    gh, capacities = BG.capacity_case(pkg, split)
+    check_capacity_mode(pkg, dev, gh, capacities, True, torch_gemm_bitwise=False)
 
 
 def test_encoder_captures(pkg, dev):
