@@ -1269,6 +1269,81 @@ int64_t scgib_collate_ws_words(int64_t batch);
 int scgib_collate_plan(const scgib_collate_desc *d, int32_t ahead, int32_t slot, int32_t advance,
                        scgib_stream_t stream);
 int scgib_collate_fill(const scgib_collate_desc *d, int32_t labels, scgib_stream_t stream);
+
+/* Device-side COO -> CSR ingest of molecule batches (ingest.hip;
+ * graph.from_coo / graph.StaticBatch.ingest).  Entry points
+ * only: the ABI version does not change.
+ *
+ * Input: src / dst [e_raw] device edge lists of idx_bytes = 4 (int32) or 8
+ * (int64) per index, graph_ptr [B+1] device int32 node offsets, n rows.
+ * Output: the dst-major CSR graph.collate_pyg gives for the same molecules —
+ * rowptr [n+1], col ascending within each row; the graph is symmetric, so one
+ * CSR serves both directions; a self-loop is kept once.
+ *   bidirect = 1: the union of the edges and their reverses, deduplicated
+ *     (dgl.to_bidirected per molecule);
+ *   bidirect = 0: the input must already be simple and symmetric; the CSR is
+ *     built and both properties are verified, not repaired.
+ * Every edge must stay inside a molecule of at most 512 atoms: row v's
+ * neighbour set is a bitmap of ceil(max_graph_nodes / 32) words relative to
+ * its molecule's first node (integer atomicOr: deterministic bits).
+ *
+ * Error bits (status[0]; OR-ed into the sticky word of the capacity form): */
+#define SCGIB_INGEST_ERANGE 1     /* an index outside [0, n), or an edge leaving its graph */
+#define SCGIB_INGEST_EGRAPH 2     /* a graph above 512 nodes */
+#define SCGIB_INGEST_ECAPACITY 4  /* a capacity exceeded */
+#define SCGIB_INGEST_ELASTNODE 8  /* skip_rule: a molecule whose last node has no edge (the
+                                     reference infers fewer nodes than x has rows and skips it) */
+#define SCGIB_INGEST_ESYMMETRY 16 /* bidirect = 0: not symmetric, or a duplicate edge */
+#define SCGIB_INGEST_ESMALL 32    /* capacity form: a molecule with fewer than two atoms */
+#define SCGIB_INGEST_EGPTR 64     /* graph_ptr is not a monotone partition of [0, n) */
+/* status (int32, scgib_ingest_status_words(B) = 16 + B + 1): [0] error bits,
+ * [1] n, [2] e = rowptr[n], [3] max in-degree, [4] / [5] smallest / largest
+ * molecule, [6..7] / [8..9] the k = 1 ego bounds as 64-bit (low, high):
+ * sum_v (1 + deg(v) - selfloop(v)) and sum_v deg(v) * (1 + deg(v) -
+ * selfloop(v)), [10] 1 when the outputs were written, [16..] graph_ptr.
+ * With any error bit set rowptr / col (or the blob) are not written.
+ *
+ * ws: scgib_ingest_workspace_bytes(rows, max_graph_nodes) bytes, zeroed once
+ * by the caller; the fill launch clears what the mark launch set (on the
+ * error path too), so it is reused without a memset.  Its layout follows
+ * `rows`: the eager entry takes the row count it was sized for as ws_rows
+ * (>= n), so one workspace serves every batch up to that size; the capacity
+ * form's is sized for n_cap.
+ *
+ * scgib_ingest_csr (eager): col_cap >= 2 * e_raw under bidirect, else e_raw.
+ * scgib_ingest_blob (capacity form, capturable): writes blob in
+ *   StaticBatch's layout (scgib_collate_desc's sections) byte for byte as
+ *   StaticBatch.pad uploads it — rowptr[n..n_cap] = e, col 0 past e,
+ *   graph_ptr, dims = [n, e, 0 (the ego error word), 0], x rows copied, 0 past
+ *   n — only if no error bit is set, n <= n_cap, e <= e_cap, the k = 1 ego
+ *   bounds within ego_n_cap / ego_e_cap, the max in-degree within
+ *   max_in_degree, every molecule of 2..max_graph_nodes atoms.  Otherwise the
+ *   blob keeps every byte and the bits are OR-ed into *sticky.  counts
+ *   (device int32 (n, e_raw), or NULL): the actual sizes, src / dst / x then
+ *   being staging buffers of e_raw indices and n_cap rows; NULL: n and e_raw
+ *   of the descriptor.  status may be NULL. */
+typedef struct {
+    const void *src, *dst;
+    const int32_t *graph_ptr;
+    const float *x;
+    const int32_t *counts;
+    void *ws;
+    int32_t *status;
+    int32_t *sticky;
+    void *blob;
+    int64_t e_raw, n;
+    int64_t n_cap, e_cap, ego_n_cap, ego_e_cap;
+    int64_t o_rowptr, o_col, o_gptr, o_dims, o_x, blob_bytes;
+    int32_t B, F, idx_bytes, max_graph_nodes, max_in_degree, bidirect, skip_rule, pad_;
+} scgib_ingest_desc;
+int64_t scgib_ingest_workspace_bytes(int64_t rows, int32_t max_graph_nodes);
+int64_t scgib_ingest_status_words(int64_t n_graphs);
+int scgib_ingest_csr(const void *src, const void *dst, int32_t idx_bytes, int64_t e_raw,
+                     const int32_t *graph_ptr, int64_t n_graphs, int64_t n_nodes,
+                     int32_t max_graph_nodes, int32_t bidirect, int32_t skip_rule, void *ws,
+                     int64_t ws_rows, int32_t *rowptr, int32_t *col, int64_t col_cap,
+                     int32_t *status, scgib_stream_t stream);
+int scgib_ingest_blob(const scgib_ingest_desc *d, scgib_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

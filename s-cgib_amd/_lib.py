@@ -214,6 +214,11 @@ SIGNATURES = {
     "scgib_collate_ws_words": (_I64, [_I64]),
     "scgib_collate_plan": (ctypes.c_int, [_P, _I32, _I32, _I32, _P]),
     "scgib_collate_fill": (ctypes.c_int, [_P, _I32, _P]),
+    "scgib_ingest_workspace_bytes": (_I64, [_I64, _I32]),
+    "scgib_ingest_status_words": (_I64, [_I64]),
+    "scgib_ingest_csr": (ctypes.c_int, [_P, _P, _I32, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P,
+                                        _I64, _P, _P, _I64, _P, _P]),
+    "scgib_ingest_blob": (ctypes.c_int, [_P, _P]),
 }
 
 
@@ -266,6 +271,29 @@ class CollateDesc(ctypes.Structure):
                   "o_gptr", "o_dims", "o_x", "blob_bytes")] +
                 [(n, ctypes.c_int32) for n in ("B", "F", "T", "pad_")])
 
+
+class IngestDesc(ctypes.Structure):
+    """scgib_ingest_desc (include/scgib.h)."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in
+                 ("src", "dst", "graph_ptr", "x", "counts", "ws", "status", "sticky", "blob")] +
+                [(n, ctypes.c_int64) for n in
+                 ("e_raw", "n", "n_cap", "e_cap", "ego_n_cap", "ego_e_cap", "o_rowptr", "o_col",
+                  "o_gptr", "o_dims", "o_x", "blob_bytes")] +
+                [(n, ctypes.c_int32) for n in
+                 ("B", "F", "idx_bytes", "max_graph_nodes", "max_in_degree", "bidirect",
+                  "skip_rule", "pad_")])
+
+
+# scgib_ingest_* error bits (SCGIB_INGEST_E* in include/scgib.h)
+INGEST_ERRORS = {
+    1: "an index outside [0, n), or an edge leaving its graph",
+    2: "a graph above 512 nodes",
+    4: "a capacity exceeded",
+    8: "a molecule whose last node has no edge",
+    16: "not symmetric, or a duplicate edge",
+    32: "a molecule with fewer than two atoms",
+    64: "graph_ptr is not a monotone partition of [0, n)",
+}
 
 ABI_VERSION = 24
 STATS_STRIDE = 260

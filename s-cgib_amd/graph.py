@@ -102,6 +102,9 @@ class GraphBatch:
         self.dims = None
         self.ego_caps = None  # (ego nodes cap, ego edges cap) for capacity mode
         self.seg_dims = None  # ego batches: device count of segments (= parent nodes)
+        # device ingest (from_coo): (max in-degree, k = 1 ego nodes, k = 1 ego edge
+        # bound) from its status record, what host_info gives a host batch
+        self.ego_k1 = None
         self.ndata = _NData(self)
         self.edata = {}
 
@@ -206,6 +209,7 @@ class GraphBatch:
         g.components_closed = self.components_closed
         g.ego_caps = self.ego_caps
         g.seg_dims = mv(self.seg_dims)
+        g.ego_k1 = self.ego_k1
         for k, v in self.ndata.items():
             dict.__setitem__(g.ndata, k, v.to(device, non_blocking=non_blocking))
         return g
@@ -364,7 +368,7 @@ def egonet_batch(g: GraphBatch, k: int, x=None):
     ego_eptr = torch.empty(n + 1, dtype=i32, device=dev)
     ws = torch.empty(int(_lib.query("scgib_egonet_workspace_bytes", n)), dtype=torch.uint8,
                      device=dev)
-    info = g.host_info
+    kb = _k1_bounds(g) if k == 1 else None
     if k == 1 and EGO_K1_FAST and n > 0:
         # two-launch k = 1 builder (sorted-list balls, batched loads): needs
         # the max in-degree bound and in-molecule edges, checked on the host
@@ -374,12 +378,10 @@ def egonet_batch(g: GraphBatch, k: int, x=None):
             caps = g.ego_caps or ()
             fast = fits and len(caps) > 2 and caps[2] <= kmax
         else:
-            fast = (fits and info is not None and info["validated"] and
-                    (len(info["deg"]) == 0 or int(info["deg"].max()) <= kmax))
+            fast = fits and kb is not None and kb[0] <= kmax
         if fast:
-            dmax = int(caps[2]) if g.dims is not None else \
-                (int(info["deg"].max()) if len(info["deg"]) else 0)
-            return _egonet_k1(g, ego_ptr, ego_eptr, ws, x, dmax)
+            dmax = int(caps[2]) if g.dims is not None else kb[0]
+            return _egonet_k1(g, ego_ptr, ego_eptr, ws, x, dmax, kb)
     err = getattr(g, "err_buf", None)
     if err is None:
         err = torch.zeros(1, dtype=i32, device=dev)
@@ -396,12 +398,10 @@ def egonet_batch(g: GraphBatch, k: int, x=None):
         n_s, e_cap = g.ego_caps[:2]
         e_s = -1
         ego_dims = torch.empty(2, dtype=i32, device=dev)
-    elif k == 1 and info is not None and info["validated"] and mgn <= 512:
+    elif k == 1 and kb is not None and mgn <= 512:
         # sizes known on the host, no device sync: |ball(v)| = 1 + deg(v) - selfloop(v);
         # the induced-edge count is bounded by sum_{u in ball(v)} deg(u)
-        ball = 1 + info["deg"] - info["selfloops"]
-        n_s = int(ball.sum())
-        e_cap = int((info["deg"] * ball).sum())
+        _, n_s, e_cap = kb
         e_s = -1  # exact count read lazily (GraphBatch.num_edges)
     else:
         tot = torch.stack([ego_ptr[n], ego_eptr[n], err[0]]).cpu().tolist()
@@ -425,6 +425,21 @@ def egonet_batch(g: GraphBatch, k: int, x=None):
     if x is not None:
         dict.__setitem__(ego.ndata, "x", x.index_select(0, ego_nodes))
     return ego
+
+
+def _k1_bounds(g):
+    """(max in-degree, ego nodes, ego edge bound) of ``g``'s k = 1 ego-nets
+    where the host knows them without a device read -- from ``host_info`` of a
+    validated host batch, or from the status record of the device ingest
+    (``from_coo``) -- else None."""
+    info = g.host_info
+    if info is not None:
+        if not info["validated"]:
+            return None
+        deg = info["deg"]
+        ball = 1 + deg - info["selfloops"]
+        return (int(deg.max()) if len(deg) else 0, int(ball.sum()), int((deg * ball).sum()))
+    return g.ego_k1
 
 
 def ego_bounds(g, k):
@@ -462,7 +477,7 @@ EGO_K1_FAST = True
 EGO_K1_ONEPASS = True
 
 
-def _egonet_k1(g, ego_ptr, ego_eptr, ws, x, max_in_degree=12):
+def _egonet_k1(g, ego_ptr, ego_eptr, ws, x, max_in_degree=12, bounds=None):
     """egonet_batch for k = 1 via scgib_egonet_k1_build (sizes known on the
     host: |ball(v)| = 1 + deg(v) - selfloop(v); capacity mode: g.ego_caps)."""
     dev = g.device
@@ -473,10 +488,7 @@ def _egonet_k1(g, ego_ptr, ego_eptr, ws, x, max_in_degree=12):
         n_s, e_cap = g.ego_caps[:2]
         ego_dims = torch.empty(2, dtype=i32, device=dev)
     else:
-        info = g.host_info
-        ball = 1 + info["deg"] - info["selfloops"]
-        n_s = int(ball.sum())
-        e_cap = int((info["deg"] * ball).sum())
+        _, n_s, e_cap = bounds if bounds is not None else _k1_bounds(g)
     ego_nodes = torch.empty(max(n_s, 1), dtype=i32, device=dev)
     sub_rowptr = torch.empty(n_s + 1, dtype=i32, device=dev)
     sub_col = torch.empty(max(e_cap, 1), dtype=i32, device=dev)
@@ -505,6 +517,182 @@ def _ego_graph(g, sub_rowptr, sub_col, ego_ptr, ego_nodes, n_s, ego_dims):
     ego.seg_dims = g.dims
     dict.__setitem__(ego.ndata, "_ID", ego_nodes[:n_s])
     return ego
+
+
+# ---------------------------------------------------------------------------
+# device-side COO -> CSR ingest (csrc/ingest.hip)
+# ---------------------------------------------------------------------------
+INGEST_MAX_GRAPH_NODES = 512  # the ingest bitmap's widest molecule (= EGO_MAX_GRAPH_NODES)
+_INGEST_WS = {}  # device -> (rows, workspace): zeroed once, the kernels reset it
+
+
+def _ingest_raise(bits, where):
+    names = "; ".join(f"{b}: {t}" for b, t in _lib.INGEST_ERRORS.items() if bits & b)
+    raise _lib.ScgibError(f"{where} flagged error bits {bits} ({names})")
+
+
+def _ingest_workspace(dev, n):
+    """(rows, workspace) of the eager ingest on ``dev`` for at least ``n``
+    rows: zero-filled when it is made or has to grow; between calls the
+    kernels leave it zero.  Its layout follows the rows it was sized for."""
+    have = _INGEST_WS.get(dev)
+    if have is None or have[0] < n:
+        nbytes = int(_lib.query("scgib_ingest_workspace_bytes", n, INGEST_MAX_GRAPH_NODES))
+        have = (n, torch.zeros(nbytes, dtype=torch.uint8, device=dev))
+        _INGEST_WS[dev] = have
+    return have
+
+
+def _index_pair(src, dst):
+    src, dst = torch.as_tensor(src), torch.as_tensor(dst)
+    if src.dtype not in (torch.int32, torch.int64):
+        src = src.to(torch.int64)
+    return src.reshape(-1).contiguous(), dst.to(src.device, src.dtype).reshape(-1).contiguous()
+
+
+def _graph_ptr_of(graph_ptr, batch_num_nodes, dev):
+    """graph_ptr as int32 [B+1] on ``dev`` (a cumsum where the per-graph counts
+    are given; no device read)."""
+    if graph_ptr is not None:
+        return torch.as_tensor(graph_ptr).reshape(-1).to(dev, torch.int32).contiguous()
+    if batch_num_nodes is None:
+        raise ValueError("from_coo: graph_ptr or batch_num_nodes is needed")
+    bnn = torch.as_tensor(batch_num_nodes).reshape(-1).to(torch.int64)
+    gp = torch.zeros(bnn.numel() + 1, dtype=torch.int64, device=bnn.device)
+    torch.cumsum(bnn, 0, out=gp[1:])
+    return gp.to(dev, torch.int32)
+
+
+def _from_coo_host(src, dst, gptr, n, bidirect, skip_rule):
+    """from_coo on the host: the device route's checks in numpy, then
+    bidirected_simple + from_edges (what collate_pyg runs)."""
+    src, dst, gptr = src.numpy().astype(np.int64), dst.numpy().astype(np.int64), \
+        gptr.numpy().astype(np.int64)
+    counts = np.diff(gptr)
+    bits = 0
+    if len(gptr) < 1 or gptr[0] != 0 or gptr[-1] != n or (counts < 0).any():
+        bits |= 64
+    if (counts > INGEST_MAX_GRAPH_NODES).any():
+        bits |= 2
+    inside = (src >= 0) & (src < n) & (dst >= 0) & (dst < n)
+    if not bits and len(counts):
+        owner = np.searchsorted(gptr, np.arange(n), side="right") - 1
+        inside[inside] &= owner[src[inside]] == owner[dst[inside]]
+    if not inside.all():
+        bits |= 1
+    if bits:
+        _ingest_raise(bits, "from_coo")
+    s, d = bidirected_simple(src, dst, max(n, 1))
+    if not bidirect:
+        key = src * max(n, 1) + dst
+        if len(s) != len(src) or not np.array_equal(np.sort(key), s * max(n, 1) + d):
+            bits |= 16  # duplicates, or an edge without its reverse
+        s, d = np.unique(key) // max(n, 1), np.unique(key) % max(n, 1)
+    deg = np.bincount(d, minlength=n)
+    if skip_rule and len(counts) and (deg[gptr[1:][counts > 0] - 1] == 0).any():
+        bits |= 8
+    if bits:
+        _ingest_raise(bits, "from_coo")
+    e_counts = np.diff(np.searchsorted(s, gptr)) if len(counts) else np.zeros(0, np.int64)
+    return GraphBatch.from_edges(s, d, n, symmetric_hint=True, batch_num_nodes=counts,
+                                 batch_num_edges=e_counts)
+
+
+def from_coo(src, dst, graph_ptr=None, num_nodes=None, x=None, bidirect=True, skip_rule=False,
+             batch_num_nodes=None):
+    """A GraphBatch from a batched COO edge list, on the tensors' device.
+
+    ``src`` / ``dst`` [E] int32 or int64 (batch-global node ids),
+    ``graph_ptr`` [B+1] node offsets or ``batch_num_nodes`` [B], ``num_nodes``
+    rows (default: ``x``'s).  ``bidirect=True``: the union of the edges and
+    their reverses, deduplicated -- ``dgl.to_bidirected`` per molecule, the CSR
+    ``collate_pyg`` gives for the same molecules, bit for bit.
+    ``bidirect=False``: the edges must already be simple and symmetric (a DGL
+    batch built by the reference's ingest, an ego batch); that is verified,
+    not repaired.  ``skip_rule``: refuse a molecule whose last atom has no
+    edge, which the reference's ingest skips (util.py:317-321).
+
+    HIP tensors go through scgib_ingest_csr (three launches) and one device ->
+    host read per batch: the status record and graph_ptr together.  The result
+    then carries the per-graph counts, the exact edge count, the largest
+    molecule and the k = 1 ego bounds, so ``egonet_batch(g, 1)`` sizes its
+    outputs without a second read.  CPU tensors take the host route with the
+    same result.  Any error bit raises ScgibError naming it
+    (``_lib.INGEST_ERRORS``)."""
+    src, dst = _index_pair(src, dst)
+    dev = src.device
+    if num_nodes is None:
+        if x is None:
+            raise ValueError("from_coo: num_nodes or x is needed")
+        num_nodes = x.shape[0]
+    n = int(num_nodes)
+    gptr = _graph_ptr_of(graph_ptr, batch_num_nodes, dev)
+    B = int(gptr.numel()) - 1
+    if src.numel() != dst.numel():
+        raise ValueError("from_coo: src and dst differ in length")
+    if dev.type != "cuda" or n == 0 or B < 1:
+        g = _from_coo_host(src.cpu(), dst.cpu(), gptr.cpu(), n, bidirect, skip_rule)
+        g = g if dev.type == "cpu" else g.to(dev)
+    else:
+        e_raw = int(src.numel())
+        col_cap = max((2 if bidirect else 1) * e_raw, 1)
+        i32 = torch.int32
+        rowptr = torch.empty(n + 1, dtype=i32, device=dev)
+        col = torch.empty(col_cap, dtype=i32, device=dev)
+        status = torch.empty(int(_lib.query("scgib_ingest_status_words", B)), dtype=i32, device=dev)
+        ws_rows, ws = _ingest_workspace(dev, n)
+        _lib.call("scgib_ingest_csr", _ptr(src), _ptr(dst), src.element_size(), e_raw, _ptr(gptr),
+                  B, n, INGEST_MAX_GRAPH_NODES, int(bool(bidirect)), int(bool(skip_rule)), _ptr(ws),
+                  ws_rows, _ptr(rowptr), _ptr(col), col_cap, _ptr(status), _stream())
+        st = status.cpu().numpy()  # the batch's one device -> host read
+        if st[0]:
+            _ingest_raise(int(st[0]), "scgib_ingest_csr")
+        e = int(st[2])
+        u64 = lambda lo, hi: (int(lo) & 0xffffffff) | ((int(hi) & 0xffffffff) << 32)  # noqa: E731
+        g = GraphBatch(rowptr, col[:e], gptr, np.diff(st[16:16 + B + 1].astype(np.int64)), None,
+                       max_graph_nodes=int(st[5]), n_edges=e)
+        g.components_closed = True  # verified by the mark launch
+        g.ego_k1 = (int(st[3]), u64(st[6], st[7]), u64(st[8], st[9]))
+    if x is not None:
+        g.ndata["x"] = x
+    return g
+
+
+def from_pyg_batch(batch, skip_rule=False):
+    """A GraphBatch from a PyG-style batch: any object with ``edge_index``
+    [2, E], ``ptr`` [B+1] and ``x`` (``from_coo`` with ``bidirect=True``;
+    ``ndata['x']`` is set)."""
+    ei = batch.edge_index
+    return from_coo(ei[0], ei[1], batch.ptr, batch.x.shape[0], x=batch.x, bidirect=True,
+                    skip_rule=skip_rule)
+
+
+def as_graph_batch(obj):
+    """``obj`` as a GraphBatch: a GraphBatch is returned as is; any other
+    object with ``edges()``, ``batch_num_nodes()`` and ``num_nodes()`` (the DGL
+    surface the reference's loops use) is converted by ``from_coo`` with
+    ``bidirect=False`` -- such a graph is already bidirected and simple, which
+    is verified -- and its ``ndata`` tensors are carried over.  The converted
+    batch is cached on the object where it accepts attributes, so a loop that
+    reuses a graph ingests it once (a graph mutated afterwards is not seen)."""
+    if isinstance(obj, GraphBatch):
+        return obj
+    cached = getattr(obj, "_scgib_graph_batch", None)
+    if cached is not None:
+        return cached
+    if not all(hasattr(obj, a) for a in ("edges", "batch_num_nodes", "num_nodes")):
+        raise TypeError(f"{type(obj).__name__} is neither a GraphBatch nor a DGL-like graph "
+                        "(edges(), batch_num_nodes(), num_nodes())")
+    src, dst = obj.edges()
+    g = from_coo(src, dst, None, int(obj.num_nodes()), bidirect=False,
+                 batch_num_nodes=obj.batch_num_nodes())
+    for key, value in dict(getattr(obj, "ndata", None) or {}).items():
+        dict.__setitem__(g.ndata, key, value)
+    try:
+        obj._scgib_graph_batch = g
+    except (AttributeError, TypeError):
+        pass
+    return g
 
 
 class StaticBatch:
@@ -608,6 +796,88 @@ class StaticBatch:
         """Copy a pad()-ed batch into the static buffers (one device copy)."""
         self.blob.copy_(padded["blob"], non_blocking=True)
         self._unload_prefetch()
+
+    def ingest(self, src, dst, graph_ptr, x, counts=None, skip_rule=False):
+        """Build a batch into the static buffers from its COO edge list on the
+        device (scgib_ingest_blob: three launches, capturable, nothing
+        allocated after the first call, nothing read back): afterwards the blob
+        holds byte for byte what ``load(pad(collate_pyg(...)))`` leaves.
+
+        ``src`` / ``dst`` [E] int32 or int64 device tensors (batch-global ids;
+        reverses and duplicates are folded as ``to_bidirected`` does),
+        ``graph_ptr`` [B+1] int32, ``x`` [n, n_feat] fp32.  ``counts=None``
+        takes n and E from the tensor shapes.  A device ``counts`` int32 [2] =
+        (n, E) makes ``src`` / ``dst`` / ``x`` capacity-sized staging buffers
+        (``x`` of at least ``n_cap`` rows) whose contents change between the
+        replays of a graph that captured this call.
+
+        A batch that does not fit (``n_cap``, ``e_cap``, the ego capacities,
+        the bitmap width), holds a molecule with fewer than two atoms or fails
+        a check leaves the blob exactly as it was; its error bits
+        (``_lib.INGEST_ERRORS``) are OR-ed into a sticky word:
+        ``ingest_error()`` / ``reset_ingest_error()``.
+
+        Limited to k = 1: the general ego builder has no capacity guard of its
+        own and the k >= 2 ego bound needs reachability, which the ingest does
+        not compute; a static batch with k >= 2 raises ScgibError."""
+        if self.k != 1:
+            raise _lib.ScgibError(f"StaticBatch.ingest is limited to k = 1 (this batch has k = "
+                                  f"{self.k}): the k >= 2 ego bounds need reachability")
+        dev = self.blob.device
+        if dev.type != "cuda":
+            raise _lib.ScgibError("StaticBatch.ingest needs a HIP device (no CPU fallback)")
+        caps = self.graph.ego_caps
+        if len(caps) < 3 or self.graph.max_graph_nodes > INGEST_MAX_GRAPH_NODES or \
+                self.graph.max_graph_nodes < 1:
+            raise _lib.ScgibError("StaticBatch.ingest needs (nodes, edges, max in-degree) ego "
+                                  f"capacities and molecules of 1..{INGEST_MAX_GRAPH_NODES} atoms")
+        i32 = torch.int32
+        ok = (src.device == dev and dst.device == dev and src.dtype == dst.dtype and
+              src.dtype in (i32, torch.int64) and src.dim() == 1 and src.shape == dst.shape and
+              src.is_contiguous() and dst.is_contiguous() and
+              graph_ptr.device == dev and graph_ptr.dtype == i32 and graph_ptr.is_contiguous() and
+              tuple(graph_ptr.shape) == (self.B + 1,) and
+              x.device == dev and x.dtype == torch.float32 and x.is_contiguous() and
+              x.dim() == 2 and x.shape[1] == self.n_feat)
+        if counts is not None:
+            ok = ok and (counts.device == dev and counts.dtype == i32 and counts.numel() >= 2 and
+                         counts.is_contiguous() and x.shape[0] >= self.n_cap)
+        if not ok:
+            raise _lib.ScgibError(
+                "StaticBatch.ingest: src / dst (int32 or int64 [E]), graph_ptr (int32 [B+1]), x "
+                "(fp32 [n, n_feat]; with counts at least n_cap rows) and counts (int32 [2]) must "
+                "be contiguous tensors on the static batch's device")
+        if getattr(self, "_ingest_ws", None) is None:
+            self._ingest_ws = torch.zeros(
+                int(_lib.query("scgib_ingest_workspace_bytes", self.n_cap,
+                               self.graph.max_graph_nodes)), dtype=torch.uint8, device=dev)
+            self._ingest_err = torch.zeros(1, dtype=i32, device=dev)
+        o = self._layout()
+        desc = _lib.IngestDesc(
+            src=src.data_ptr(), dst=dst.data_ptr(), graph_ptr=graph_ptr.data_ptr(),
+            x=x.data_ptr(), counts=None if counts is None else counts.data_ptr(),
+            ws=self._ingest_ws.data_ptr(), status=None, sticky=self._ingest_err.data_ptr(),
+            blob=self.blob.data_ptr(), e_raw=int(src.numel()), n=int(x.shape[0]),
+            n_cap=self.n_cap, e_cap=self.e_cap, ego_n_cap=int(caps[0]), ego_e_cap=int(caps[1]),
+            o_rowptr=o[0], o_col=o[1], o_gptr=o[2], o_dims=o[3], o_x=o[4],
+            blob_bytes=self.blob.numel(), B=self.B, F=self.n_feat, idx_bytes=src.element_size(),
+            max_graph_nodes=self.graph.max_graph_nodes, max_in_degree=min(int(caps[2]), 1 << 30),
+            bidirect=1, skip_rule=int(bool(skip_rule)), pad_=0)
+        # (a captured graph reads these buffers at every replay: keep them alive)
+        self._ingest_keep = (src, dst, graph_ptr, x, counts)
+        _lib.call("scgib_ingest_blob", ctypes.byref(desc), _stream())
+        self._unload_prefetch()
+
+    def ingest_error(self):
+        """The sticky error bits of the ingests so far (0 = none;
+        ``_lib.INGEST_ERRORS``) -- a device read, for outside the loop."""
+        err = getattr(self, "_ingest_err", None)
+        return 0 if err is None else int(err.item())
+
+    def reset_ingest_error(self):
+        err = getattr(self, "_ingest_err", None)
+        if err is not None:
+            err.zero_()
 
     def _unload_prefetch(self):
         pf = getattr(self.graph, "ego_prefetch", None)

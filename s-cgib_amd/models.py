@@ -34,6 +34,11 @@ Differences from the reference, all deliberate:
     graph (the query it would feed cancels in the per-graph softmax) and a
     Mainmodel_continue around a model of the other readout width is refused
     when it is built (DESIGN.md §16);
+  * ``batch_g`` and ``flatten_batch_subgraphs`` may be any DGL-like graph
+    (``edges()``, ``batch_num_nodes()``, ``num_nodes()``, ``ndata``): the four
+    model classes pass them through ``graph.as_graph_batch`` once, at the top
+    of ``forward`` / ``extract_features``; a ``graph.GraphBatch`` goes through
+    untouched;
   * ``flatten_batch_subgraphs`` may be ``None``: the ego-nets are then built
     on the device from ``batch_g`` (scgib_egonet_*), replacing the offline
     khop_in_subgraph pass and the per-step dgl.batch of the reference;
@@ -753,6 +758,9 @@ class Mainmodel(_SCGIBCore):
     @ops.aside_guard
     def extract_features(self, nodes_list, batch_g, batch_x, flatten_batch_subgraphs, x_subs,
                          device=None, noise=None):
+        batch_g = G.as_graph_batch(batch_g)
+        if flatten_batch_subgraphs is not None:
+            flatten_batch_subgraphs = G.as_graph_batch(flatten_batch_subgraphs)
         ego, x_subs = self._prepare_ego(batch_g, flatten_batch_subgraphs, batch_x, x_subs)
         im, kl, noisy, z2, z1 = self._extract(self, batch_g, batch_x, ego, x_subs, noise)
         self._last_z1 = z1
@@ -764,6 +772,9 @@ class Mainmodel(_SCGIBCore):
                 current_epoch=None, edge_index=None, k_transition=None, device=None,
                 batch_size=16, noise=None):
         self.batch_size = batch_size
+        batch_g = G.as_graph_batch(batch_g)
+        if flatten_batch_subgraphs is not None:
+            flatten_batch_subgraphs = G.as_graph_batch(flatten_batch_subgraphs)
         if flatten_batch_subgraphs is None and x_subs is None and batch_x.is_cuda:
             ego, enc = self._encode_forked(self, batch_g, batch_x, FORK_ENCODERS,
                                            noise is None)
@@ -841,6 +852,9 @@ class Mainmodel_continue(_SCGIBCore):
     @ops.aside_guard
     def extract_features(self, nodes_list, batch_g, batch_x, flatten_batch_subgraphs, x_subs,
                          device=None, noise=None):
+        batch_g = G.as_graph_batch(batch_g)
+        if flatten_batch_subgraphs is not None:
+            flatten_batch_subgraphs = G.as_graph_batch(flatten_batch_subgraphs)
         ego, x_subs = self._prepare_ego(batch_g, flatten_batch_subgraphs, batch_x, x_subs)
         im, kl, noisy, z2, z1 = self._extract(self, batch_g, batch_x, ego, x_subs, noise)
         self._last_z1 = z1
@@ -857,6 +871,9 @@ class Mainmodel_continue(_SCGIBCore):
                 current_epoch=None, edge_index=None, k_transition=None, device=None,
                 batch_size=16, noise=None):
         self.batch_size = batch_size
+        batch_g = G.as_graph_batch(batch_g)
+        if flatten_batch_subgraphs is not None:
+            flatten_batch_subgraphs = G.as_graph_batch(flatten_batch_subgraphs)
         if flatten_batch_subgraphs is None and x_subs is None and batch_x.is_cuda:
             # the wrapper's transfer_d feeds the wrapped model's encoders
             ego, enc = self._encode_forked(self.model, batch_g, batch_x, FORK_ENCODERS,
@@ -949,6 +966,9 @@ class Mainmodel_domainadapt(_SCGIBCore):
                          device=None, noise=None):
         """models.py:283-335: the DA model's own encoders / compressor /
         attention (what fine-tuning on an adapted checkpoint runs)."""
+        batch_g = G.as_graph_batch(batch_g)
+        if flatten_batch_subgraphs is not None:
+            flatten_batch_subgraphs = G.as_graph_batch(flatten_batch_subgraphs)
         ego, x_subs = self._prepare_ego(batch_g, flatten_batch_subgraphs, batch_x, x_subs)
         im, kl, noisy, z2, z1 = self._extract(self, batch_g, batch_x, ego, x_subs, noise)
         self._last_z1 = z1
@@ -962,6 +982,9 @@ class Mainmodel_domainadapt(_SCGIBCore):
         self.batch_size = batch_size
         self.device = device
         batch_x_org = batch_x
+        batch_g = G.as_graph_batch(batch_g)
+        if flatten_batch_subgraphs is not None:
+            flatten_batch_subgraphs = G.as_graph_batch(flatten_batch_subgraphs)
         inner = self.model
         if flatten_batch_subgraphs is None and x_subs is None and batch_x.is_cuda:
             # this model's transfer_d feeds the pretrained model's encoders
@@ -1057,6 +1080,9 @@ class Mainmodel_finetuning(nn.Module):
                 edge_index=None, k_transition=None, device=None, batch_size=2, noise=None):
         self.batch_size = batch_size
         self.device = device
+        batch_g = G.as_graph_batch(batch_g)
+        if flatten_batch_subgraphs is not None:
+            flatten_batch_subgraphs = G.as_graph_batch(flatten_batch_subgraphs)
         inner = self.model
         if flatten_batch_subgraphs is None and x_subs is None and batch_x.is_cuda and \
                 isinstance(inner, _SCGIBCore):
