@@ -1229,7 +1229,9 @@ int scgib_eval_scan(const int64_t *sorted, int64_t n_rows, int32_t n_tasks, int3
  * The sequence: perm [2][M] holds the permutations of epochs of even and odd
  * number; state[0] is the position j in [0, 2S) (S batches of B per epoch),
  * state[1] the sticky count of batches that did not fit.  Batch j is
- * perm[j / S][(j % S) * B .. + B).
+ * perm[j / S][(j % S) * B .. + B).  perm holds molecule ids below D, the
+ * dataset's molecule count (D = 0: below M), so a loader over a subset of a
+ * larger dataset has M = the subset's length and D = the dataset's.
  * The ring: srcs = table of three slot pointers, each blob_bytes long in
  * StaticBatch's layout (sections rowptr [n_cap+1], col [max(e_cap,1)],
  * graph_ptr [B+1], dims [4], x [n_cap][F] at the byte offsets o_*, multiples
@@ -1262,13 +1264,35 @@ typedef struct {
     int64_t M, S;
     int64_t n_cap, e_cap, ego_n_cap, ego_e_cap;
     int64_t o_rowptr, o_col, o_gptr, o_dims, o_x, blob_bytes;
-    int32_t B, F, T, pad_;
+    int32_t B, F, T;
+    int32_t D; /* molecules in the dataset, which bounds the ids in perm; 0 = M */
 } scgib_collate_desc;
 int64_t scgib_collate_max_batch(void);
 int64_t scgib_collate_ws_words(int64_t batch);
 int scgib_collate_plan(const scgib_collate_desc *d, int32_t ahead, int32_t slot, int32_t advance,
                        scgib_stream_t stream);
 int scgib_collate_fill(const scgib_collate_desc *d, int32_t labels, scgib_stream_t stream);
+
+/* Sequential batches of an index list over the same dataset, ring and
+ * descriptor (collate.hip; graph.DeviceEvalLoader).  Entry
+ * points only: the ABI version does not change.
+ *
+ * The sequence lives in device memory, so that a captured graph serves one
+ * list after another: perm [M] is the index list's buffer (M its capacity, D
+ * >= 1 the dataset's molecule count, S unused) and state [4] = position, sticky
+ * overflow count, list length len in 1..M, fill molecule id.  One pass has
+ * steps = ceil(len / B) batches; batch j holds perm[j*B .. min((j+1)*B, len))
+ * followed by copies of the fill molecule, and the position is cyclic.
+ *
+ * scgib_collate_seq_plan: as scgib_collate_plan for batch (state[0] + ahead) mod
+ *   steps, ahead in 0..2.  slot_ids gets the ids of the list's rows and -1 for
+ *   fill rows; a batch that does not fit sets all B ids of its slot to -1
+ *   (and bumps state[1]).  advance: state[0] = (state[0] + 1) mod steps.
+ * scgib_collate_seq_fill: as scgib_collate_fill; a row whose slot id is
+ *   negative gets a label row of NaN and id -1. */
+int scgib_collate_seq_plan(const scgib_collate_desc *d, int32_t ahead, int32_t slot,
+                           int32_t advance, scgib_stream_t stream);
+int scgib_collate_seq_fill(const scgib_collate_desc *d, int32_t labels, scgib_stream_t stream);
 
 /* Device-side COO -> CSR ingest of molecule batches (ingest.hip;
  * graph.from_coo / graph.StaticBatch.ingest).  Entry points

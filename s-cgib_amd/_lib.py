@@ -214,6 +214,8 @@ SIGNATURES = {
     "scgib_collate_ws_words": (_I64, [_I64]),
     "scgib_collate_plan": (ctypes.c_int, [_P, _I32, _I32, _I32, _P]),
     "scgib_collate_fill": (ctypes.c_int, [_P, _I32, _P]),
+    "scgib_collate_seq_plan": (ctypes.c_int, [_P, _I32, _I32, _I32, _P]),
+    "scgib_collate_seq_fill": (ctypes.c_int, [_P, _I32, _P]),
     "scgib_ingest_workspace_bytes": (_I64, [_I64, _I32]),
     "scgib_ingest_status_words": (_I64, [_I64]),
     "scgib_ingest_csr": (ctypes.c_int, [_P, _P, _I32, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P,
@@ -269,7 +271,7 @@ class CollateDesc(ctypes.Structure):
                 [(n, ctypes.c_int64) for n in
                  ("M", "S", "n_cap", "e_cap", "ego_n_cap", "ego_e_cap", "o_rowptr", "o_col",
                   "o_gptr", "o_dims", "o_x", "blob_bytes")] +
-                [(n, ctypes.c_int32) for n in ("B", "F", "T", "pad_")])
+                [(n, ctypes.c_int32) for n in ("B", "F", "T", "D")])
 
 
 class IngestDesc(ctypes.Structure):

@@ -22,6 +22,14 @@
 // which a section's words would pass the next section or the slot.  On
 // overflow (fits == 0) the fill writes nothing to the slot.  Integer work
 // only: deterministic.  Index arithmetic into the dataset arrays is 64-bit.
+//
+// The sequential loader (graph.DeviceEvalLoader) runs the same
+// two bodies over another batch sequence: collate_seq_plan_k takes batch j of
+// an index list whose length, fill molecule and position sit in device memory
+// (state[0] position, [1] overflow count, [2] list length, [3] fill id), the
+// rows past the list's end being copies of the fill molecule with id -1;
+// collate_seq_fill_k gathers NaN labels and id -1 for those rows.  There an
+// overflowing batch marks its slot's ids -1 as well.
 #include <algorithm>
 
 #include "common.h"
@@ -51,21 +59,32 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
     return v;
 }
 
-// blockDim.x = the multiple of 64 covering ceil(B / kPlanItems) threads
-__global__ __launch_bounds__(kPlanThreads) void collate_plan_k(scgib_collate_desc d, int32_t ahead,
-                                                               int32_t slot_fixed,
-                                                               int32_t advance) {
+// blockDim.x = the multiple of 64 covering ceil(B / kPlanItems) threads.
+// kSeq: the sequential loader's batch j = (position + ahead) mod steps of the
+// index list d.perm[0 .. state[2]) (state[2] clamped to 1 .. d.M, its capacity).
+template <bool kSeq>
+__device__ __forceinline__ void plan_body(const scgib_collate_desc &d, int32_t ahead,
+                                          int32_t slot_fixed, int32_t advance) {
     __shared__ int s_wn[kPlanThreads / kWave], s_we[kPlanThreads / kWave];
     __shared__ unsigned long long s_gn[kPlanThreads / kWave], s_ge[kPlanThreads / kWave];
     __shared__ int s_fits;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const int nwaves = blockDim.x / kWave;
-    const int64_t S2 = 2 * d.S;
+    const int64_t D = d.D > 0 ? d.D : d.M;  // molecules in the dataset
+    // the position's period: the two-epoch window, or the steps of one pass
+    int64_t len = d.M, fill = 0, S2 = 2 * d.S;
+    if (kSeq) {
+        len = static_cast<int64_t>(d.state[2]);
+        len = len < 1 ? 1 : (len > d.M ? d.M : len);
+        fill = static_cast<int64_t>(d.state[3]);  // (clamped with the other ids below)
+        S2 = (len + d.B - 1) / d.B;
+    }
     const int64_t pos = static_cast<int64_t>(d.state[0]) % S2;
     const unsigned cur = d.cursor[0];
     const int64_t j = (pos + ahead) % S2;
-    // batch j of the two-epoch window: permutation buffer j / S, offset (j % S) * B
-    const int64_t base = (j / d.S) * d.M + (j % d.S) * d.B;
+    // batch j of the two-epoch window: permutation buffer j / S, offset (j % S) * B;
+    // batch j of the index list: offset j * B
+    const int64_t base = kSeq ? j * d.B : (j / d.S) * d.M + (j % d.S) * d.B;
 
     int id[kPlanItems], nn[kPlanItems], ee[kPlanItems];
     int64_t nb[kPlanItems], eb[kPlanItems];
@@ -78,9 +97,10 @@ __global__ __launch_bounds__(kPlanThreads) void collate_plan_k(scgib_collate_des
         nn[q] = ee[q] = 0;
         nb[q] = eb[q] = 0;
         if (i < d.B) {
-            int64_t m = d.perm[base + i];
-            m = m < 0 ? 0 : (m >= d.M ? d.M - 1 : m);  // (host-written; never out of range)
-            id[q] = static_cast<int>(m);
+            const bool real = !kSeq || base + i < len;  // else a copy of the fill molecule
+            int64_t m = real ? d.perm[base + i] : fill;
+            m = m < 0 ? 0 : (m >= D ? D - 1 : m);  // (host-written; never out of range)
+            id[q] = real ? static_cast<int>(m) : -1;
             nb[q] = d.node_off[m];
             eb[q] = d.edge_off[m];
             nn[q] = static_cast<int>(d.node_off[m + 1] - nb[q]);
@@ -144,11 +164,27 @@ __global__ __launch_bounds__(kPlanThreads) void collate_plan_k(scgib_collate_des
             eoff[i] = off_e;
             nbase[i] = nb[q];
             ebase[i] = eb[q];
-            if (fits) ids[i] = id[q];  // an overflowing batch leaves the slot's ids too
+            // an overflowing batch leaves the slot's ids too; in a sequential
+            // pass it marks them: the step that scores the stale bytes labels nothing
+            if (fits) ids[i] = id[q];
+            else if (kSeq) ids[i] = -1;
         }
         off_n += nn[q];
         off_e += ee[q];
     }
+}
+
+__global__ __launch_bounds__(kPlanThreads) void collate_plan_k(scgib_collate_desc d, int32_t ahead,
+                                                               int32_t slot_fixed,
+                                                               int32_t advance) {
+    plan_body<false>(d, ahead, slot_fixed, advance);
+}
+
+__global__ __launch_bounds__(kPlanThreads) void collate_seq_plan_k(scgib_collate_desc d,
+                                                                   int32_t ahead,
+                                                                   int32_t slot_fixed,
+                                                                   int32_t advance) {
+    plan_body<true>(d, ahead, slot_fixed, advance);
 }
 
 // largest m in [0, B) with ptr[m] <= v, for 0 <= v < ptr[B] (ptr[0] = 0)
@@ -177,8 +213,10 @@ __device__ __forceinline__ void find4(const int *ptr, int B, int64_t v0, int64_t
     }
 }
 
-__global__ __launch_bounds__(256) void collate_fill_k(scgib_collate_desc d, int32_t labels) {
-    extern __shared__ __attribute__((aligned(16))) int s_ptr[];  // gptr [B+1] | eoff [B+1]
+// kMasked: a negative slot id (a fill row, or a slot whose batch overflowed in
+// a sequential pass) gets a label row of NaN and id -1 instead of y[id].
+template <bool kMasked>
+__device__ __forceinline__ void fill_body(const scgib_collate_desc &d, int32_t labels, int *s_ptr) {
     const int B = d.B, F = d.F, T = d.T;
     // staged whatever the plan found: the header's loads stay in flight beside these
     for (int i = threadIdx.x; i < 2 * (B + 1); i += blockDim.x) s_ptr[i] = d.ws[kWsHead + i];
@@ -212,7 +250,8 @@ __global__ __launch_bounds__(256) void collate_fill_k(scgib_collate_desc d, int3
         for (int l = gtid; l < nl + B; l += stride) {
             if (l < nl) {
                 const int64_t id = cur_ids[l / T];
-                d.labels[l] = d.y[id * T + l % T];
+                if (kMasked && id < 0) d.labels[l] = __builtin_nanf("");
+                else d.labels[l] = d.y[id * T + l % T];
             } else {
                 d.ids[l - nl] = cur_ids[l - nl];
             }
@@ -299,15 +338,27 @@ __global__ __launch_bounds__(256) void collate_fill_k(scgib_collate_desc d, int3
     if (gtid == stride - 1) *reinterpret_cast<int4 *>(slot + d.o_dims) = make_int4(n, e, 0, 0);
 }
 
-static bool desc_ok(const scgib_collate_desc *d) {
+__global__ __launch_bounds__(256) void collate_fill_k(scgib_collate_desc d, int32_t labels) {
+    extern __shared__ __attribute__((aligned(16))) int s_ptr[];  // gptr [B+1] | eoff [B+1]
+    fill_body<false>(d, labels, s_ptr);
+}
+
+__global__ __launch_bounds__(256) void collate_seq_fill_k(scgib_collate_desc d, int32_t labels) {
+    extern __shared__ __attribute__((aligned(16))) int s_ptr[];  // gptr [B+1] | eoff [B+1]
+    fill_body<true>(d, labels, s_ptr);
+}
+
+// seq: a sequential loader's descriptor (M = the index list's capacity, S unused)
+static bool desc_ok(const scgib_collate_desc *d, bool seq = false) {
     if (!d) return false;
     if (!d->node_off || !d->edge_off || !d->rp_local || !d->col || !d->x || !d->ego_nodes ||
         !d->ego_edges || !d->perm || !d->srcs || !d->cursor || !d->state || !d->ws ||
         !d->slot_ids || !d->ids)
         return false;
-    if (d->B < 1 || d->B > kMaxBatch || d->M < 1 || d->S < 1 || d->S * d->B > d->M || d->F < 1 ||
-        d->T < 0 || (d->T > 0 && (!d->y || !d->labels)))
+    if (d->B < 1 || d->B > kMaxBatch || d->M < 1 || d->F < 1 || d->T < 0 ||
+        (d->T > 0 && (!d->y || !d->labels)))
         return false;
+    if (seq ? d->D < 1 : (d->D < 0 || d->S < 1 || d->S * d->B > d->M)) return false;
     const int64_t lim = (int64_t{1} << 31) - 8;
     if (d->n_cap < 0 || d->e_cap < 0 || d->ego_n_cap < 0 || d->ego_e_cap < 0 || d->n_cap >= lim ||
         d->e_cap >= lim || d->n_cap * d->F >= lim)
@@ -337,14 +388,33 @@ extern "C" int scgib_collate_plan(const scgib_collate_desc *d, int32_t ahead, in
     return launch_status();
 }
 
-extern "C" int scgib_collate_fill(const scgib_collate_desc *d, int32_t labels,
-                                  scgib_stream_t stream) {
-    if (!desc_ok(d)) return SCGIB_EINVAL;
+static int launch_fill(const scgib_collate_desc *d, int32_t labels, bool seq,
+                       scgib_stream_t stream) {
+    if (!desc_ok(d, seq)) return SCGIB_EINVAL;
     const int64_t quads = (d->n_cap + 1 + 3) / 4 + (std::max<int64_t>(d->e_cap, 1) + 3) / 4 +
                           (d->B + 1 + 3) / 4 + 1 + (d->n_cap * d->F + 3) / 4;
     const int64_t total = quads + (labels ? static_cast<int64_t>(d->B) * d->T + d->B : 0);
     const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 2048));
     const size_t lds = sizeof(int) * 2 * (static_cast<size_t>(d->B) + 1);
-    collate_fill_k<<<(unsigned)grid, 256, lds, as_stream(stream)>>>(*d, labels ? 1 : 0);
+    if (seq) collate_seq_fill_k<<<(unsigned)grid, 256, lds, as_stream(stream)>>>(*d, labels ? 1 : 0);
+    else collate_fill_k<<<(unsigned)grid, 256, lds, as_stream(stream)>>>(*d, labels ? 1 : 0);
     return launch_status();
+}
+
+extern "C" int scgib_collate_fill(const scgib_collate_desc *d, int32_t labels,
+                                  scgib_stream_t stream) {
+    return launch_fill(d, labels, false, stream);
+}
+
+extern "C" int scgib_collate_seq_plan(const scgib_collate_desc *d, int32_t ahead, int32_t slot,
+                                      int32_t advance, scgib_stream_t stream) {
+    if (!desc_ok(d, true) || ahead < 0 || ahead > 2 || slot < -1 || slot > 2) return SCGIB_EINVAL;
+    const int threads = ((d->B + kPlanItems - 1) / kPlanItems + kWave - 1) / kWave * kWave;
+    collate_seq_plan_k<<<1, threads, 0, as_stream(stream)>>>(*d, ahead, slot, advance ? 1 : 0);
+    return launch_status();
+}
+
+extern "C" int scgib_collate_seq_fill(const scgib_collate_desc *d, int32_t labels,
+                                      scgib_stream_t stream) {
+    return launch_fill(d, labels, true, stream);
 }

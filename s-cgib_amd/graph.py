@@ -1342,18 +1342,40 @@ class DeviceDataset:
         return cls(np.concatenate([[0], np.cumsum(counts)]), np.concatenate(degs),
                    np.concatenate(cols), np.concatenate(xs), y, device, k, drop_single_atom)
 
-    def capacities(self, B, mode="worst", slack=1.0, samples=64, seed=0):
+    def capacities(self, B, mode="worst", slack=1.0, samples=64, seed=0, indices=None):
         """The tuple StaticBatch.capacities returns, for batches of ``B``
         molecules of this dataset.  ``"worst"``: the sums of the B largest
         per-molecule node, edge and ego values, so no batch can overflow.
         ``"sampled"``: the maxima over ``samples`` seeded random batches times
         ``slack``, as StaticBatch.capacities takes them over host batches; a
-        batch above them is skipped by the loader (DeviceLoader.error)."""
+        batch above them is skipped by the loader (DeviceLoader.error).
+        ``"sequential"``: the exact maxima (no slack, nothing added) over
+        every batch a DeviceEvalLoader builds from ``indices`` -- one id list
+        or a list of id lists, default the whole dataset -- the last batch's
+        fill rows included, so one static batch sized this way serves each of
+        the subsets and cannot overflow."""
         B = int(B)
-        if not 1 <= B <= self.num_graphs:
-            raise _lib.ScgibError(f"capacities: batch size {B} outside 1..{self.num_graphs}")
         per = [self.node_counts, self.edge_counts, self.host["ego_nodes"].astype(np.int64),
                self.host["ego_edges"].astype(np.int64)]
+        dmax = self.max_in_degree if self.k == 1 else 1 << 30
+        if mode == "sequential":
+            if B < 1:
+                raise _lib.ScgibError(f"capacities: batch size {B} below 1")
+            if indices is None:
+                subsets = [np.arange(self.num_graphs)]
+            elif len(indices) and np.ndim(indices[0]) > 0:
+                subsets = list(indices)
+            else:
+                subsets = [indices]
+            tops = [0, 0, 0, 0]
+            for sub in subsets:
+                ids = sequential_ids(self, sub, B)[0]
+                tops = [max(t, int(v[ids].sum(axis=1).max())) for t, v in zip(tops, per)]
+            return tops[0], tops[1], self.max_graph_nodes, (tops[2], tops[3], dmax)
+        if indices is not None:
+            raise ValueError("capacities: indices go with mode \"sequential\"")
+        if not 1 <= B <= self.num_graphs:
+            raise _lib.ScgibError(f"capacities: batch size {B} outside 1..{self.num_graphs}")
         if mode == "worst":
             tops = [int(np.sort(v)[-B:].sum()) for v in per]
         elif mode == "sampled":
@@ -1363,9 +1385,9 @@ class DeviceDataset:
                 ids = rng.choice(self.num_graphs, B, replace=False)
                 tops = [max(t, int(v[ids].sum())) for t, v in zip(tops, per)]
         else:
-            raise ValueError(f"capacities: mode {mode!r} (\"worst\" or \"sampled\")")
+            raise ValueError(f"capacities: mode {mode!r} (\"worst\", \"sampled\" or "
+                             "\"sequential\")")
         f = lambda v: int(v * slack) + 1  # noqa: E731
-        dmax = self.max_in_degree if self.k == 1 else 1 << 30
         return f(tops[0]), f(tops[1]), self.max_graph_nodes, (f(tops[2]), f(tops[3]), dmax)
 
 
@@ -1414,6 +1436,106 @@ def collate_blob_host(host, ids, static):
     return blob, labels, ids.astype(np.int32)
 
 
+def _subset_ids(dataset, indices, who):
+    """``indices`` (None: every molecule) as a checked int64 id list."""
+    if indices is None:
+        return np.arange(dataset.num_graphs, dtype=np.int64)
+    ids = np.asarray(indices)
+    if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+        raise _lib.ScgibError(f"{who}: indices must be a 1-D integer array of molecule ids")
+    if ids.size == 0:
+        raise _lib.ScgibError(f"{who}: an empty subset")
+    ids = ids.astype(np.int64)
+    if ids.min() < 0 or ids.max() >= dataset.num_graphs:
+        bad = ids[(ids < 0) | (ids >= dataset.num_graphs)][0]
+        raise _lib.ScgibError(f"{who}: molecule id {int(bad)} outside 0..{dataset.num_graphs - 1}")
+    return ids
+
+
+def sequential_fill_id(dataset, indices):
+    """The molecule a DeviceEvalLoader fills the last batch of ``indices`` up
+    with: the subset's smallest by atom count, then edge count, then id."""
+    ids = _subset_ids(dataset, indices, "sequential_fill_id")
+    order = np.lexsort((ids, dataset.edge_counts[ids], dataset.node_counts[ids]))
+    return int(ids[order[0]])
+
+
+def sequential_ids(dataset, indices, B):
+    """The sequential batches of ``indices`` as (molecule ids [steps, B] with
+    the fill molecule in the rows past the list's end, the same with -1
+    there): what DeviceEvalLoader collates and what it reports in ``ids``."""
+    ids = _subset_ids(dataset, indices, "sequential_ids")
+    B = int(B)
+    steps = -(-len(ids) // B)
+    pad = steps * B - len(ids)
+    rows = np.concatenate([ids, np.full(pad, sequential_fill_id(dataset, ids), np.int64)])
+    marked = np.concatenate([ids, np.full(pad, -1, np.int64)])
+    return rows.reshape(steps, B), marked.reshape(steps, B)
+
+
+def sequential_blob_host(dataset, indices, j, static):
+    """Batch ``j`` of the sequential batches of ``indices`` through
+    collate_blob_host: (blob, labels with NaN rows at the fill positions or
+    None, ids int32 with -1 there)."""
+    rows, marked = sequential_ids(dataset, indices, static.B)
+    blob, labels, _ = collate_blob_host(dataset.host, rows[j], static)
+    if labels is not None:
+        labels = labels.copy()
+        labels[marked[j] < 0] = np.nan
+    return blob, labels, marked[j].astype(np.int32)
+
+
+def _loader_checks(who, ds, static):
+    """What both loaders ask of a static batch; returns (ego caps, device)."""
+    B = int(static.B)
+    if not 1 <= B <= COLLATE_MAX_BATCH:
+        raise _lib.ScgibError(f"{who}: batch size {B} outside 1..{COLLATE_MAX_BATCH}")
+    caps = static.graph.ego_caps or ()
+    if len(caps) < 2:
+        raise _lib.ScgibError(f"{who}: the static batch has no ego capacities")
+    if static.n_feat != ds.num_features or static.k != ds.k:
+        raise _lib.ScgibError(f"{who}: static batch and dataset differ in feature "
+                              "width or ego radius k")
+    if ds.max_graph_nodes > static.graph.max_graph_nodes:
+        raise _lib.ScgibError(f"{who}: the dataset has a larger molecule than the "
+                              "static batch's bitmap width")
+    if len(caps) > 2 and ds.max_in_degree > caps[2]:
+        raise _lib.ScgibError(f"{who}: the dataset's max in-degree exceeds the "
+                              "static batch's ego builder bound")
+    dev = static.blob.device
+    if ds.device != dev:
+        raise _lib.ScgibError(f"{who}: dataset and static batch on different devices")
+    return caps, dev
+
+
+def _loader_ring(static, dev):
+    """(ring, slots, pool): three blobs of ``static``'s layout in one
+    allocation, as the pool StaticBatch.pool returns."""
+    nbytes = static.blob.numel()
+    ring = torch.zeros(3 * nbytes, dtype=torch.uint8, device=dev)
+    slots = [ring[i * nbytes:(i + 1) * nbytes] for i in range(3)]
+    pool = {"table": torch.tensor([s.data_ptr() for s in slots], dtype=torch.int64, device=dev),
+            "cursor": torch.zeros(2, dtype=torch.int32, device=dev), "n": 3,
+            "batches": [{"blob": s} for s in slots]}
+    return ring, slots, pool
+
+
+def _collate_desc(ds, static, caps, loader, M, S):
+    a = ds.arrays
+    o = static._layout()
+    p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    return _lib.CollateDesc(
+        node_off=p(a["node_off"]), edge_off=p(a["edge_off"]), rp_local=p(a["rp_local"]),
+        col=p(a["col"]), x=p(a["x"]), y=p(a["y"]), ego_nodes=p(a["ego_nodes"]),
+        ego_edges=p(a["ego_edges"]), perm=p(loader.perm), srcs=p(loader.pool["table"]),
+        cursor=p(loader.pool["cursor"]), state=p(loader.state), ws=p(loader._ws),
+        slot_ids=p(loader._slot_ids), labels=p(loader.labels), ids=p(loader.ids), M=M, S=S,
+        n_cap=static.n_cap, e_cap=static.e_cap, ego_n_cap=int(caps[0]), ego_e_cap=int(caps[1]),
+        o_rowptr=o[0], o_col=o[1], o_gptr=o[2], o_dims=o[3], o_x=o[4],
+        blob_bytes=static.blob.numel(), B=int(static.B), F=ds.num_features, T=ds.num_tasks,
+        D=ds.num_graphs)
+
+
 class DeviceLoader:
     """Shuffled batches of a DeviceDataset collated on the device, one step
     ahead of a replayed step over ``static`` (csrc/collate.hip).
@@ -1425,7 +1547,9 @@ class DeviceLoader:
     ``collate_ahead()`` — enqueued after load_next — builds batch t + 2 into
     slot (t + 2) % 3, the slot neither of them touches.
 
-    Batch sequence: S = M // B steps per epoch (S >= 3); global batch j holds
+    Batch sequence: M molecules -- the whole dataset, or the subset
+    ``indices`` (molecule ids, repeats allowed) -- in S = M // B steps per
+    epoch (S >= 3); global batch j holds
     molecules ``epoch_permutation(j // S)[(j % S) * B : + B]``.  The M % B
     molecules at the end of each permutation are dropped that epoch (the
     reference trains on the partial batch; a captured graph has a fixed B).
@@ -1441,41 +1565,20 @@ class DeviceLoader:
     the earlier batch, labels and ids follow the slot) and counted:
     ``error()``."""
 
-    def __init__(self, dataset, static, seed=0, shuffle=True):
+    def __init__(self, dataset, static, seed=0, shuffle=True, indices=None):
         ds = dataset
-        B, M = int(static.B), ds.num_graphs
-        if not 1 <= B <= COLLATE_MAX_BATCH:
-            raise _lib.ScgibError(f"DeviceLoader: batch size {B} outside 1..{COLLATE_MAX_BATCH}")
+        caps, dev = _loader_checks("DeviceLoader", ds, static)
+        self.indices = None if indices is None else _subset_ids(ds, indices, "DeviceLoader")
+        B, M = int(static.B), ds.num_graphs if indices is None else len(self.indices)
         S = M // B
         if S < 3:
             raise _lib.ScgibError(f"DeviceLoader: {M} molecules give {S} batches of {B} per epoch; "
                                   "the three-slot ring needs at least 3")
-        caps = static.graph.ego_caps or ()
-        if len(caps) < 2:
-            raise _lib.ScgibError("DeviceLoader: the static batch has no ego capacities")
-        if static.n_feat != ds.num_features or static.k != ds.k:
-            raise _lib.ScgibError("DeviceLoader: static batch and dataset differ in feature "
-                                  "width or ego radius k")
-        if ds.max_graph_nodes > static.graph.max_graph_nodes:
-            raise _lib.ScgibError("DeviceLoader: the dataset has a larger molecule than the "
-                                  "static batch's bitmap width")
-        if len(caps) > 2 and ds.max_in_degree > caps[2]:
-            raise _lib.ScgibError("DeviceLoader: the dataset's max in-degree exceeds the "
-                                  "static batch's ego builder bound")
-        dev = static.blob.device
-        if ds.device != dev:
-            raise _lib.ScgibError("DeviceLoader: dataset and static batch on different devices")
         self.dataset, self.static = ds, static
         self.seed, self.shuffle = int(seed), bool(shuffle)
         self.B, self.M, self.steps_per_epoch = B, M, S
-        nbytes = static.blob.numel()
-        self.ring = torch.zeros(3 * nbytes, dtype=torch.uint8, device=dev)
-        self.slots = [self.ring[i * nbytes:(i + 1) * nbytes] for i in range(3)]
+        self.ring, self.slots, self.pool = _loader_ring(static, dev)
         i32 = torch.int32
-        self.pool = {"table": torch.tensor([s.data_ptr() for s in self.slots], dtype=torch.int64,
-                                           device=dev),
-                     "cursor": torch.zeros(2, dtype=i32, device=dev), "n": 3,
-                     "batches": [{"blob": s} for s in self.slots]}
         T = ds.num_tasks
         self.labels = torch.zeros(B, T, dtype=torch.float32, device=dev)
         self.ids = torch.zeros(B, dtype=i32, device=dev)
@@ -1485,26 +1588,18 @@ class DeviceLoader:
         self._ws = torch.zeros((8 + 2 * (B + 1) + 1) // 2 * 2 + 4 * B, dtype=i32, device=dev)
         self._slot_ids = torch.zeros(3 * B, dtype=i32, device=dev)
         self._pinned = [None, None]  # begin_epoch's host staging and its copy's event
-        a = ds.arrays
-        o = static._layout()
-        p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
-        self._desc = _lib.CollateDesc(
-            node_off=p(a["node_off"]), edge_off=p(a["edge_off"]), rp_local=p(a["rp_local"]),
-            col=p(a["col"]), x=p(a["x"]), y=p(a["y"]), ego_nodes=p(a["ego_nodes"]),
-            ego_edges=p(a["ego_edges"]), perm=p(self.perm), srcs=p(self.pool["table"]),
-            cursor=p(self.pool["cursor"]), state=p(self.state), ws=p(self._ws),
-            slot_ids=p(self._slot_ids), labels=p(self.labels), ids=p(self.ids), M=M, S=S,
-            n_cap=static.n_cap, e_cap=static.e_cap, ego_n_cap=int(caps[0]), ego_e_cap=int(caps[1]),
-            o_rowptr=o[0], o_col=o[1], o_gptr=o[2], o_dims=o[3], o_x=o[4], blob_bytes=nbytes,
-            B=B, F=ds.num_features, T=T, pad_=0)
+        self._desc = _collate_desc(ds, static, caps, self, M, S)
 
     # ----- the batch sequence (host side) ---------------------------------
     def epoch_permutation(self, e):
         """perm_e on the host (int64 numpy): drawn from a CPU generator seeded
-        by (seed, e); the identity without shuffling."""
+        by (seed, e); the identity without shuffling.  Over a subset
+        (``indices``) the same permutation of its positions, as molecule ids."""
         if not self.shuffle:
-            return np.arange(self.M, dtype=np.int64)
-        return np.random.default_rng([self.seed, int(e)]).permutation(self.M).astype(np.int64)
+            perm = np.arange(self.M, dtype=np.int64)
+        else:
+            perm = np.random.default_rng([self.seed, int(e)]).permutation(self.M).astype(np.int64)
+        return perm if self.indices is None else self.indices[perm]
 
     def batch_ids(self, j):
         """Molecule ids of global batch j (begin_epoch called every epoch)."""
@@ -1580,4 +1675,113 @@ class DeviceLoader:
     def error(self):
         """How many batches did not fit the capacities and were skipped
         (sticky) — a device read, for checks outside the loop."""
+        return int(self.state[1].item())
+
+
+class DeviceEvalLoader:
+    """The molecules of a subset of a DeviceDataset in order, every one exactly
+    once per pass, collated on the device one step ahead of a replayed
+    evaluation step over ``static`` (csrc/collate.hip).
+
+    ``pool`` / ``labels`` / ``ids`` / ``error()`` as on DeviceLoader:
+    ``static.load_next(evl.pool, pf)`` and ``EgoPrefetch(static, evl.pool)``
+    consume the ring unchanged, and ``labels`` / ``ids`` describe the batch the
+    step scores for work enqueued after ``collate_ahead()`` on its stream.
+
+    Batch sequence: ``steps = ceil(M / B)`` (any steps >= 1); batch j holds
+    ``indices[j * B : min((j + 1) * B, M)]`` in order and step t, counted from
+    ``prime()``, scores batch t % steps.  The last batch is filled up to B with
+    copies of the subset's smallest molecule (``sequential_fill_id``), so the
+    step sees an ordinary batch; fill rows have ``ids`` -1 and a label row of
+    NaN, which ops.task_loss and EvalBuffer ignore.  After ``steps`` steps
+    the position is 0 again and the next pass needs no host call.
+
+    A batch above the capacities of ``static`` is not written and counted
+    (``error()``); its slot's ids become -1, so the step that scores the slot's
+    stale bytes reports only NaN-labelled rows.  ``static`` sized by
+    ``dataset.capacities(B, "sequential", indices=...)`` cannot overflow.
+
+    The list, its length, the fill id and the position live in device memory:
+    ``set_subset(indices)`` (up to ``max_len`` ids, default the first list's
+    length) points a graph captured over the loader at another subset."""
+
+    def __init__(self, dataset, static, indices=None, max_len=None):
+        ds = dataset
+        caps, dev = _loader_checks("DeviceEvalLoader", ds, static)
+        ids = _subset_ids(ds, indices, "DeviceEvalLoader")
+        self.max_len = len(ids) if max_len is None else int(max_len)
+        if len(ids) > self.max_len:
+            raise _lib.ScgibError(f"DeviceEvalLoader: {len(ids)} indices above max_len "
+                                  f"{self.max_len}")
+        self.dataset, self.static = ds, static
+        B = self.B = int(static.B)
+        self.ring, self.slots, self.pool = _loader_ring(static, dev)
+        i32 = torch.int32
+        self.labels = torch.zeros(B, ds.num_tasks, dtype=torch.float32, device=dev)
+        self.ids = torch.zeros(B, dtype=i32, device=dev)
+        # position in [0, steps), overflow count, list length, fill molecule id
+        self.state = torch.zeros(4, dtype=i32, device=dev)
+        self.perm = torch.zeros(self.max_len, dtype=i32, device=dev)  # the index list
+        self._ws = torch.zeros((8 + 2 * (B + 1) + 1) // 2 * 2 + 4 * B, dtype=i32, device=dev)
+        self._slot_ids = torch.zeros(3 * B, dtype=i32, device=dev)
+        self._desc = _collate_desc(ds, static, caps, self, self.max_len, 1)
+        self._set_host(ids)
+
+    def _set_host(self, ids):
+        self.indices, self.M = ids, len(ids)
+        self.steps = -(-self.M // self.B)
+        self.fill_id = sequential_fill_id(self.dataset, ids)
+
+    def batch_ids(self, j):
+        """(molecule ids collated into batch j % steps, fill included; the ids
+        the loader reports for it, -1 at the fill rows)."""
+        rows, marked = sequential_ids(self.dataset, self.indices, self.B)
+        return rows[j % self.steps], marked[j % self.steps]
+
+    def _launch(self, ahead, slot, advance, labels):
+        d = ctypes.byref(self._desc)
+        _lib.call("scgib_collate_seq_plan", d, ahead, slot, advance, _stream())
+        _lib.call("scgib_collate_seq_fill", d, labels, _stream())
+
+    def set_subset(self, indices):
+        """Eager, on the current stream, between passes: the index list, its
+        length and fill id, position 0, cursor 0 and batches 0, 1, 2 (mod
+        steps) into slots 0, 1, 2.  The caller re-primes its EgoPrefetch; a
+        graph captured over the loader then scores the new subset.  The
+        overflow count is kept; a primed batch that does not fit raises."""
+        ids = _subset_ids(self.dataset, indices, "DeviceEvalLoader.set_subset")
+        if len(ids) > self.max_len:
+            raise _lib.ScgibError(f"DeviceEvalLoader.set_subset: {len(ids)} indices above "
+                                  f"max_len {self.max_len}")
+        if self.ring.device.type != "cuda":
+            raise _lib.ScgibError("DeviceEvalLoader needs a HIP device (no CPU fallback)")
+        self._set_host(ids)
+        before = self.error()
+        self.perm[:self.M].copy_(torch.from_numpy(ids.astype(np.int32)))
+        self.state.copy_(torch.tensor([0, before, self.M, self.fill_id], dtype=torch.int32))
+        self.pool["cursor"].zero_()
+        for slot in (0, 1, 2):
+            self._launch(slot, slot, 0, 0)
+        if self.error() != before:
+            raise _lib.ScgibError("DeviceEvalLoader: the first batches do not fit the "
+                                  "capacities of the static batch")
+
+    def prime(self):
+        """Eager, before the capture: ``set_subset`` of the current indices
+        with the overflow count reset."""
+        if self.ring.device.type != "cuda":
+            raise _lib.ScgibError("DeviceEvalLoader.prime needs a HIP device (no CPU fallback)")
+        self.state.zero_()
+        self.set_subset(self.indices)
+
+    def collate_ahead(self):
+        """Once per step after load_next, on a stream ordered after it
+        (capturable; no host synchronisation): batch (t + 2) % steps into slot
+        (cursor + 1) % 3, batch t's labels and ids into ``labels`` / ``ids``,
+        and the position moves on (cyclic)."""
+        self._launch(2, -1, 1, 1)
+
+    def error(self):
+        """How many batches did not fit the capacities (sticky) — a device
+        read, for checks outside the loop."""
         return int(self.state[1].item())
