@@ -868,6 +868,46 @@ int scgib_task_loss_fwd(const float *scores, const float *targets, int64_t n, in
 int scgib_task_loss_bwd(const float *scores, const float *targets, int64_t n, int32_t kind,
                         int32_t mask_nan, const float *g_loss, const float *loss,
                         const int32_t *count, float *d_scores, scgib_stream_t stream);
+/* ---- Class-index cross-entropy and TU accuracy (csrc/class_loss.hip) -------
+ * (Entry points added to ABI 24: nothing existing changes.)
+ * loss_CrossEntropy (models.py:527-530: F.cross_entropy on the scores and the
+ * class column, train_tudataset.py:146, :205) and accuracy_TU
+ * (metrics.py:146-159) in one launch.  scores [n_rows, n_classes] fp32 row
+ * major; labels [n_rows] class indices of type label_type:
+ *     SCGIB_LABEL_F32  masked when NaN (the device loaders' fill rows)
+ *     SCGIB_LABEL_I32 / _I64  masked when -100 (torch's ignore_index)
+ * A label that is neither masked nor an integer in [0, n_classes) (1.5, -1,
+ * n_classes, +-inf) makes the row invalid: counted in *invalid, no loss, no
+ * hit, no count, zero gradient, and it indexes nothing.  Per kept row, fp32:
+ *     l_r = log(sum_c exp(s_rc - m_r)) + m_r - s_ry,  m_r the row maximum
+ * (torch's log_softmax + nll); a row's hit: its argmax equals y, with torch's
+ * argmax order (a NaN above every number, the lowest index among equals).
+ * loss = sum l_r / count, NaN when count = 0; the sum is fp64 in a fixed
+ * order (a group of 2, 8, 32 or 64 lanes per row by n_classes, a wavefront's
+ * rows by a fixed butterfly and its sweeps in order, the four wavefronts of a
+ * workgroup in order, at most 64 workgroups in workgroup order by the last to
+ * arrive; one workgroup — up to 128 rows of two classes — writes the outputs
+ * itself and touches neither ws nor counter).  ws:
+ * scgib_class_loss_ws_doubles() doubles,
+ * 8-byte aligned; counter: one zeroed uint32, left zero.  epoch (or NULL): 5
+ * doubles { sum of loss, batches, hits, labelled, invalid }: a batch with a
+ * kept row adds its loss, 1, hits and count; every batch adds invalid (one
+ * thread; launches on one stream are ordered).
+ * Backward, from g_loss (device scalar) and the forward's count:
+ *     d s_rc = g (softmax(s_r)_c - [c = y_r]) / count
+ * at kept rows, the softmax recomputed from the scores; exactly 0 at masked
+ * and invalid rows and everywhere when count = 0.
+ * 1 <= n_classes <= 1024 and 1 <= n_rows <= 2^30, otherwise SCGIB_EINVAL /
+ * SCGIB_EUNSUPPORTED and nothing is launched. */
+enum { SCGIB_LABEL_F32 = 0, SCGIB_LABEL_I32 = 1, SCGIB_LABEL_I64 = 2 };
+int64_t scgib_class_loss_ws_doubles(void);
+int scgib_class_loss_fwd(const float *scores, const void *labels, int32_t label_type,
+                         int64_t n_rows, int32_t n_classes, double *ws, uint32_t *counter,
+                         float *loss, int32_t *count, int32_t *hits, int32_t *invalid,
+                         double *epoch, scgib_stream_t stream);
+int scgib_class_loss_bwd(const float *scores, const void *labels, int32_t label_type,
+                         int64_t n_rows, int32_t n_classes, const float *g_loss,
+                         const int32_t *count, float *d_scores, scgib_stream_t stream);
 /* Backward of scgib_interaction_fwd.  The KL gradient is g_kl [2 n_last, 64],
  * or g_klmean (device scalar, gradient of kl_mean), or neither (both NULL);
  * g_z1 / g_z2 may be NULL (readouts that feed no loss: zero gradient).

@@ -42,6 +42,10 @@ SIGNATURES = {
     "scgib_task_loss_ws_doubles": (_I64, []),
     "scgib_task_loss_fwd": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     "scgib_task_loss_bwd": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
+    "scgib_class_loss_ws_doubles": (_I64, []),
+    "scgib_class_loss_fwd": (ctypes.c_int, [_P, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _P,
+                                            _P]),
+    "scgib_class_loss_bwd": (ctypes.c_int, [_P, _P, _I32, _I64, _I32, _P, _P, _P, _P]),
     "scgib_pool_copy": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P]),
     "scgib_pool_copy2": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P, _I64, _P]),
     "scgib_stream_signal": (ctypes.c_int, [_P, _P]),

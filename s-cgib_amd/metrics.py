@@ -14,7 +14,8 @@
   accuracy_TU   metrics.py:146-159 (argmax over classes, count of matches)
 Host-side (numpy / sklearn / torch CPU ops), as in the reference; pinned by
 tests/golden/metrics.npz (oracle/gen_metrics_golden.py runs the reference's
-own functions).
+own functions).  ClassEpoch keeps accuracy_TU's count and the epoch loss of the
+TU loops on the device (ops.class_loss).
 """
 from __future__ import annotations
 
@@ -188,3 +189,47 @@ class EvalBuffer:
         if (t[6] == 0).any():
             raise ZeroDivisionError("float division by zero")
         return {"acc": sum(float(v) for v in t[3]) / self.num_tasks}
+
+
+class ClassEpoch:
+    """Epoch totals of a TU graph-classification loop (train_tudataset.py:
+    137-158, :196-221) kept on the device.
+
+    ``ops.class_loss(scores, labels, epoch=self)`` adds each batch in the
+    loss's own launch: the batch loss (``epoch_loss += loss.detach().item()``),
+    one to the batch count, the accuracy_TU count of the batch and its
+    labelled rows (``nb_data += targets.size(0)``).  Nothing synchronises, so
+    the step captures and every replay adds the batch that is in the static
+    inputs at that moment; ``result`` is the epoch's single read.  Rows
+    without a label (NaN / -100: the fill rows of DeviceEvalLoader's last
+    batch) count nowhere, so the last batch's mean is the mean over its real
+    molecules — the reference's short last batch."""
+
+    def __init__(self, device):
+        from . import _lib, ops
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.ScgibError(f"ClassEpoch: device {device}; the accumulator lives on the HIP "
+                                  "device only (no CPU fallback)")
+        # sum of loss, batches, hits, labelled, invalid
+        self.state = torch.zeros(ops.CLASS_EPOCH_DOUBLES, dtype=torch.float64, device=device)
+
+    def reset(self):
+        """Totals back to zero (a device memset; capturable)."""
+        self.state.zero_()
+
+    def result(self):
+        """``{"loss": sum of batch losses / batches, "acc": hits / labelled,
+        "hits", "labelled", "batches"}`` — ``epoch_loss /= (iter + 1)`` and
+        ``epoch_acc /= nb_data``.  Synchronises (one read).  Raises ScgibError
+        when a label was neither masked nor a class index, ZeroDivisionError
+        when no row was labelled."""
+        from . import _lib
+        loss, batches, hits, labelled, invalid = self.state.cpu().tolist()
+        if invalid > 0:
+            raise _lib.ScgibError(f"ClassEpoch: {int(invalid)} labels that are neither masked nor "
+                                  "a class index in [0, C)")
+        if labelled == 0:
+            raise ZeroDivisionError("float division by zero")
+        return {"loss": loss / batches, "acc": hits / labelled, "hits": int(hits),
+                "labelled": int(labelled), "batches": int(batches)}

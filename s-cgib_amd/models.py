@@ -438,6 +438,11 @@ DEVICE_NOISE = True
 # heads (C > 16), the MAE / RMSE / BCE-with-logits losses and MetricWrapper's
 # NaN-masked "ignore-flatten" losses on csrc/task_head.hip
 FUSE_HEAD = True
+# loss_CrossEntropy on integer HIP targets through ops.class_loss
+# (csrc/class_loss.hip) instead of F.cross_entropy.  Off by default: integer
+# targets keep torch's bits.  float32 HIP targets — what the
+# device loaders carry, which F.cross_entropy refuses — take the kernel always.
+DEVICE_CE = False
 # readout_f != "sum": the step's two Set2Set readouts (noisy and plain graph
 # features, one LSTM) as one autograd node and one launch per direction
 # (ops.set2set_pair); off: two ops.set2set calls (tools/readout_bench.py's A/B)
@@ -1125,7 +1130,16 @@ class Mainmodel_finetuning(nn.Module):
             return ops.bce_mean(scores.float(), targets.float())  # one launch each way
         return F.binary_cross_entropy(scores.float(), targets.float())
 
-    def loss_CrossEntropy(self, scores, targets):
+    def loss_CrossEntropy(self, scores, targets, epoch=None):
+        """models.py:527-530.  ``epoch``: a metrics.ClassEpoch that the device
+        loss adds this batch to (the torch path has no such accumulator)."""
+        if scores.is_cuda and targets.is_cuda and (
+                targets.dtype == torch.float32 or
+                (DEVICE_CE and targets.dtype in (torch.int32, torch.int64))):
+            return ops.class_loss(scores, targets, epoch=epoch)  # one launch each way
+        if epoch is not None:
+            raise ops._lib.ScgibError("loss_CrossEntropy: epoch= needs the device loss (float32 HIP "
+                                  "targets, or integer ones with models.DEVICE_CE)")
         return F.cross_entropy(scores.to(torch.float32), targets.squeeze(dim=-1))
 
     def loss_RMSE(self, scores, targets):

@@ -1840,6 +1840,87 @@ def task_loss(scores, targets, kind, ignore_nan=True, return_count=False):
     return (loss, count) if return_count else loss
 
 
+# class-index cross-entropy (csrc/class_loss.hip; SCGIB_LABEL_* in include/scgib.h)
+CLASS_LABEL_TYPES = {torch.float32: 0, torch.int32: 1, torch.int64: 2}
+CLASS_EPOCH_DOUBLES = 5  # sum of loss, batches, hits, labelled, invalid
+
+
+def _class_scratch(dev):
+    """The arrival counter and the fp64 partials of scgib_class_loss_fwd, both
+    from the call site's ``counters`` range: word 0 is the counter (left zero),
+    the partials follow at the next 8-byte boundary (rewritten by every
+    launch before they are read)."""
+    words = 2 * int(_lib.query("scgib_class_loss_ws_doubles"))
+    c = counters(dev, "class_loss", words + 2)
+    ws = c[1:] if (c.data_ptr() + 4) % 8 == 0 else c[2:]
+    return c, ws
+
+
+class _ClassLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, y, epoch):
+        dev = s.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        stats = torch.empty(3, dtype=torch.int32, device=dev)  # count, hits, invalid
+        counter, ws = _class_scratch(dev)
+        ltype = CLASS_LABEL_TYPES[y.dtype]
+        _lib.call("scgib_class_loss_fwd", _p(s), _p(y), ltype, s.shape[0], s.shape[1], _p(ws),
+                  _p(counter), _p(loss), _p(stats[0]), _p(stats[1]), _p(stats[2]),
+                  _p(epoch), _stream())
+        ctx.save_for_backward(s, y, stats)
+        ctx.ltype = ltype
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, g, _g_stats):
+        s, y, stats = ctx.saved_tensors
+        ds = torch.empty_like(s)
+        _lib.call("scgib_class_loss_bwd", _p(s), _p(y), ctx.ltype, s.shape[0], s.shape[1],
+                  _p(_f32(g.reshape(1), "class loss grad")), _p(stats), _p(ds), _stream())
+        return ds, None, None
+
+
+def class_loss(scores, labels, epoch=None, return_stats=False):
+    """``F.cross_entropy(scores, labels)`` over class indices (models.py:527-530)
+    and the batch's accuracy_TU count (metrics.py:146-159) in one launch each
+    way.  ``scores`` [B, C] fp32, 1 <= C <= HEAD_C_MAX; ``labels`` [B] or
+    [B, 1], float32 (a NaN masks the row: the device loaders' fill rows),
+    int32 or int64 (-100 masks the row: torch's ignore_index).  The mean is
+    over the kept rows; none kept: the loss is NaN and the gradient zero.  A
+    label that is neither masked nor an integer in [0, C) makes its row
+    invalid: it is counted, adds no loss, no hit and no gradient, and indexes
+    nothing.  ``epoch``: the state of a metrics.ClassEpoch (or the object),
+    which the same launch adds this batch to.  ``return_stats``: also the
+    int32 device scalars count, hits (rows whose argmax — torch's: the lowest
+    index among the maxima, a NaN above every number — equals the label) and
+    invalid.  Nothing synchronises, so the step captures; the first call per
+    device and stream must be outside graph capture (``counters``)."""
+    if not (scores.is_cuda and labels.is_cuda):
+        raise _lib.ScgibError(f"class_loss: scores on {scores.device}, labels on {labels.device}; "
+                              "the S-CGIB ops run on the HIP device only (no CPU fallback)")
+    if labels.dtype not in CLASS_LABEL_TYPES:
+        raise _lib.ScgibError(f"class_loss: labels of {labels.dtype}; float32, int32 or int64 "
+                              "class indices")
+    if scores.dim() != 2 or scores.numel() == 0:
+        raise _lib.ScgibError(f"class_loss: scores {tuple(scores.shape)}; a non-empty [B, C]")
+    b, c = scores.shape
+    if tuple(labels.shape) not in ((b,), (b, 1)):
+        raise _lib.ScgibError(f"class_loss: scores {tuple(scores.shape)} vs labels "
+                              f"{tuple(labels.shape)}")
+    if c > HEAD_C_MAX:
+        raise _lib.ScgibError(f"class_loss: {c} classes; at most {HEAD_C_MAX}")
+    state = getattr(epoch, "state", epoch)
+    if state is not None and not (state.is_cuda and state.dtype == torch.float64
+                                  and state.numel() == CLASS_EPOCH_DOUBLES
+                                  and state.is_contiguous() and state.device == scores.device):
+        raise _lib.ScgibError("class_loss: epoch is not a metrics.ClassEpoch state on the "
+                              "scores' device")
+    loss, stats = _ClassLoss.apply(_f32(scores, "class loss scores"),
+                                   labels.reshape(b).contiguous(), state)
+    return (loss, stats[0], stats[1], stats[2]) if return_stats else loss
+
+
 # ---------------------------------------------------------------------------
 # A6-A8: fused core <-> subgraph interaction
 # ---------------------------------------------------------------------------
