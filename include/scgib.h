@@ -606,7 +606,8 @@ int scgib_set2set_bwd2(const float *xa, const float *xb, const int32_t *graph_pt
  * scalar kernel, e.g. for raw node features). */
 int scgib_segment_sum(const float *x, const int32_t *ptr, int64_t n_seg, int32_t dim,
                       float *out, const int32_t *dims, scgib_stream_t stream);
-/* n_rows: rows of `out` (rows past ptr[actual n_seg] are zeroed in capacity mode) */
+/* n_rows: rows of `out` (rows past ptr[actual n_seg] are zeroed, with or without
+ * device dims: every row of `out` is written) */
 int scgib_segment_broadcast(const float *g, const int32_t *ptr, int64_t n_seg, int32_t dim,
                             float *out, int64_t n_rows, const int32_t *dims,
                             scgib_stream_t stream);

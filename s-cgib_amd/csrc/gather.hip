@@ -87,7 +87,10 @@ __global__ __launch_bounds__(256) void segment_broadcast_k(const float4 *__restr
     const int64_t s = blk * RPB + threadIdx.x / LPR;
     const int c = threadIdx.x % LPR;
     const int64_t ns = eff_count(dims, 0, nseg);
-    if (dims) {  // zero the rows past the last valid segment (grid-stride)
+    {  // zero the rows past the last valid segment (grid-stride): the spare
+       // segments' rows under device dims, and a capacity batch's padded rows
+       // behind a fixed segment count (dims null: the per-graph readout of a
+       // StaticBatch), as segment_broadcast_scalar_k does
         const int64_t r0 = ptr[ns];
         const int64_t tot = (nrows - r0) * LPR;
         for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < tot;
