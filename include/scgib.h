@@ -1157,6 +1157,24 @@ int scgib_mlp2_recon_contrastive_bwd(const float *x, const float *r, const float
 int64_t scgib_linear_slab_floats(int64_t n_nodes);
 int scgib_linear_fwd(const float *x, int64_t n_nodes, const float *w, const float *b, float *out,
                      const int32_t *dims, scgib_stream_t stream);
+/* The encoder output's BatchNorm + ReLU with compressor[0] behind it, one
+ * launch (csrc/dense.hip; an entry point only: the ABI version stays 24, as
+ * for the other entries added since).  Replaces scgib_bn_relu_apply followed
+ * by scgib_linear_fwd on its output, where the encoder pair folds
+ * compressor[0] (models.py:596 / :1092 after GIN.forward's last BatchNorm +
+ * ReLU, :66-72):
+ *   f_out = relu(scale z2 + shift),  t_out = f_out w0^T (+ b0, may be NULL)
+ * [n_nodes][64] each, bitwise the two entries' results.  scale / shift come
+ * from `stat` ([4][64] record), or, with `pending` (may be NULL; n_nodes <=
+ * scgib_gin_defer_max_nodes()), from the last layer's deferred statistics:
+ * finished here, the record and the running statistics are then written
+ * exactly once.  One 64-row tile per workgroup; the f tile stays in LDS
+ * between the two steps.  dims (may be NULL): rows >= dims[0] of both
+ * outputs are zeros, and every element up to n_nodes is written. */
+int scgib_enc_out_linear_fwd(const float *z2, const float *stat, int64_t n_nodes,
+                             const float *w0, const float *b0, float *f_out, float *t_out,
+                             const int32_t *dims, const scgib_bn_pending *pending,
+                             scgib_stream_t stream);
 /* wgrad NULL: the slabs (scgib_linear_slab_floats(n) floats, width 64*64 + 64)
  * are left for the caller's reduce. */
 int scgib_linear_bwd(const float *dy, const float *x, const float *w, int64_t n_nodes,

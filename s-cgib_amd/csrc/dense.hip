@@ -8,6 +8,7 @@
 // workgroup (fixed-order slab reduce after), dx = [add +] dy W per tile —
 // `add` folds the other gradient of x (the interaction's d f) into the same
 // pass.  Capacity mode (dims): rows >= dims[0] are written as zeros.
+#include "gin_bn.h"
 #include "mfma_tile.h"
 
 namespace scgib {
@@ -52,6 +53,88 @@ __global__ __launch_bounds__(256) void linear_fwd_k(const float *__restrict__ x,
     for (int reg = 0; reg < 16; ++reg) {
         const int row = wr * 32 + acc_row(reg, l);
         if (row < nv) out[(row0 + row) * 64 + ccol] = acc[reg] + bias;
+    }
+}
+
+// The encoder output's BatchNorm + ReLU and compressor[0] in one launch:
+//   f = relu(scale z2 + shift)  (bn_relu_apply_k),  t = f W^T + b  (linear_fwd_k)
+// one 64-row tile per workgroup; the f tile goes to f_out and stays in LDS as
+// the product's A operand, so f is not read back and one launch leaves the
+// chain.  Same xform4 and the same MFMA chain over the same operands as the
+// two kernels: f and t are bitwise theirs.
+// Load order: the deferred statistics' group partials, gamma and beta (pend)
+// or the record's scale / shift (stat) first, then the tile's z2 rows and W —
+// neither waits for the statistics — and only then the finish.  With pend,
+// every workgroup finishes the statistics and workgroup 0 writes the record
+// and the running update (bn_pending_finish).  Capacity mode: rows >= dims[0]
+// are zeros in both outputs; a tile of padding rows only writes them (and, as
+// workgroup 0, still finishes the statistics).
+__global__ __launch_bounds__(256) void enc_out_linear_fwd_k(
+    const float *__restrict__ z, const float *__restrict__ stat, int64_t ncap,
+    const float *__restrict__ w, const float *__restrict__ b, float *__restrict__ f_out,
+    float *__restrict__ t_out, const int32_t *__restrict__ dims, scgib_bn_pending pend) {
+    __shared__ float sA[TM * LDH];
+    __shared__ float sW[64 * LDH];
+    __shared__ float sSS[128];
+    const int64_t n = eff_count(dims, 0, ncap);
+    const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6, wr = wv >> 1, wc = wv & 1;
+    const int r0 = tid >> 4, cq = tid & 15, c = 4 * cq;  // rows r0 + 16 k, one channel quad
+    const int64_t row0 = static_cast<int64_t>(blockIdx.x) * TM;
+    const int nv = static_cast<int>(n - row0 < TM ? (n - row0 > 0 ? n - row0 : 0) : TM);
+    const int ncr = static_cast<int>(ncap - row0 < TM ? ncap - row0 : TM);
+    // (block-uniform) a padding tile takes part in the finish only as workgroup 0
+    const bool fin = pend.gpart && (nv > 0 || blockIdx.x == 0);
+    PendFin pf;
+    float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), sh = sc;
+    if (fin) {
+        bn_pending_load(pend, n, pf);
+    } else if (!pend.gpart) {
+        sc = ld4(stat + 128 + c);
+        sh = ld4(stat + 192 + c);
+    }
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 v[4], wq[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int rr = r0 + 16 * k;
+        v[k] = ld_ok(reinterpret_cast<const float4 *>(z), (row0 + rr) * 16 + cq, row0 * 16 + cq,
+                     rr < nv, z4);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wq[k] = reinterpret_cast<const float4 *>(w)[tid + 256 * k];
+    const float bias = b ? b[wc * 32 + (l & 31)] : 0.f;
+    // padding rows of both outputs (capacity mode; ncr == nv otherwise)
+    for (int idx = nv * 64 + tid; idx < ncr * 64; idx += 256) {
+        f_out[row0 * 64 + idx] = 0.f;
+        t_out[row0 * 64 + idx] = 0.f;
+    }
+    if (fin) {
+        bn_pending_finish(pend, n, pf, sSS);
+        sc = make_float4(sSS[c], sSS[c + 1], sSS[c + 2], sSS[c + 3]);
+        sh = make_float4(sSS[64 + c], sSS[65 + c], sSS[66 + c], sSS[67 + c]);
+    }
+    if (nv == 0) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int rr = r0 + 16 * k;
+        const float4 f = rr < nv ? xform4(v[k], sc, sh) : z4;
+        if (rr < nv) st4(f_out + (row0 + rr) * 64 + c, f);
+        float *d = sA + rr * LDH + c;
+        d[0] = f.x; d[1] = f.y; d[2] = f.z; d[3] = f.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {  // stage_matrix<64>'s layout
+        const int idx = 4 * (tid + 256 * k), row = idx >> 6, cc = idx & 63;
+        float *d = sW + row * LDH + cc;
+        d[0] = wq[k].x; d[1] = wq[k].y; d[2] = wq[k].z; d[3] = wq[k].w;
+    }
+    __syncthreads();
+    const int ccol = wc * 32 + (l & 31);
+    f32x16 acc = mma_nt<64>(sA + wr * 32 * LDH, LDH, sW + wc * 32 * LDH, LDH, zero16());
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int row = wr * 32 + acc_row(reg, l);
+        if (row < nv) t_out[(row0 + row) * 64 + ccol] = acc[reg] + bias;
     }
 }
 
@@ -147,6 +230,23 @@ extern "C" int scgib_linear_fwd(const float *x, int64_t n_nodes, const float *w,
     if (!x || !w || !out) return SCGIB_EINVAL;
     const unsigned grid = static_cast<unsigned>((n_nodes + TM - 1) / TM);
     linear_fwd_k<<<grid, 256, 0, as_stream(stream)>>>(x, w, b, n_nodes, out, dims);
+    return launch_status();
+}
+
+extern "C" int scgib_enc_out_linear_fwd(const float *z2, const float *stat, int64_t n_nodes,
+                                        const float *w0, const float *b0, float *f_out,
+                                        float *t_out, const int32_t *dims,
+                                        const scgib_bn_pending *pending, scgib_stream_t stream) {
+    if (n_nodes < 0) return SCGIB_EINVAL;
+    if (n_nodes == 0) return SCGIB_OK;
+    if (!z2 || !w0 || !f_out || !t_out || (!stat && !pending)) return SCGIB_EINVAL;
+    if (pending && (!pending->gpart || !pending->gamma || !pending->beta || !pending->stat ||
+                    ((pending->running_mean == nullptr) != (pending->running_var == nullptr)) ||
+                    n_nodes > scgib_gin_defer_max_nodes()))
+        return SCGIB_EINVAL;
+    const unsigned grid = static_cast<unsigned>((n_nodes + TM - 1) / TM);
+    enc_out_linear_fwd_k<<<grid, 256, 0, as_stream(stream)>>>(
+        z2, stat, n_nodes, w0, b0, f_out, t_out, dims, pending ? *pending : scgib_bn_pending{});
     return launch_status();
 }
 

@@ -183,17 +183,33 @@ __device__ __forceinline__ float2 bn_fwd_publish(int c, double mean, double M2, 
 // statistics from the group partials; workgroup 0 writes the record and the
 // running update.  sSS[c] = scale, sSS[64 + c] = shift.  Call from all
 // threads, before any early return.
-__device__ __forceinline__ void bn_pending_finish(const scgib_bn_pending &pend, int64_t n,
-                                                  float *sSS) {
-    const int fc = fin_channel();
-    const int ngr = static_cast<int>(((n + TM - 1) / TM + kGroup - 1) / kGroup);
-    const float gam = pend.gamma[fc], bet = pend.beta[fc];
+// Split into the loads (bn_pending_load: the first round of group partials,
+// gamma and beta — issue it first, then the caller's own independent loads)
+// and the finish, so a tile kernel keeps its rows in flight across the finish.
+struct PendFin {
     FwdFin fin;
-    bn_fwd_fin_load<false>(pend.gpart, ngr, 0, fin);
+    float gam, bet;
+};
+
+__device__ __forceinline__ int pending_groups(int64_t n) {
+    return static_cast<int>(((n + TM - 1) / TM + kGroup - 1) / kGroup);
+}
+
+__device__ __forceinline__ void bn_pending_load(const scgib_bn_pending &pend, int64_t n,
+                                                PendFin &r) {
+    const int fc = fin_channel();
+    r.gam = pend.gamma[fc];
+    r.bet = pend.beta[fc];
+    bn_fwd_fin_load<false>(pend.gpart, pending_groups(n), 0, r.fin);
+}
+
+__device__ __forceinline__ void bn_pending_finish(const scgib_bn_pending &pend, int64_t n,
+                                                  PendFin &r, float *sSS) {
+    const int fc = fin_channel();
     double mean, M2;
-    bn_fwd_final<false>(pend.gpart, n, ngr, fin, mean, M2);
+    bn_fwd_final<false>(pend.gpart, n, pending_groups(n), r.fin, mean, M2);
     const bool lead = (threadIdx.x & 63) < 16;
-    const float2 ss = bn_fwd_publish(fc, mean, M2, n, gam, bet, pend.eps, pend.momentum,
+    const float2 ss = bn_fwd_publish(fc, mean, M2, n, r.gam, r.bet, pend.eps, pend.momentum,
                                      pend.running_mean, pend.running_var,
                                      pend.num_batches_tracked, pend.stat, blockIdx.x == 0 && lead);
     if (lead) {
@@ -201,6 +217,13 @@ __device__ __forceinline__ void bn_pending_finish(const scgib_bn_pending &pend, 
         sSS[64 + fc] = ss.y;
     }
     __syncthreads();
+}
+
+__device__ __forceinline__ void bn_pending_finish(const scgib_bn_pending &pend, int64_t n,
+                                                  float *sSS) {
+    PendFin r;
+    bn_pending_load(pend, n, r);
+    bn_pending_finish(pend, n, r, sSS);
 }
 
 // 256 threads: channel c = tid & 63, partition p = tid >> 6 (4 partitions).

@@ -79,6 +79,12 @@ AGG_FREE = True
 # (the d = 64 forward 0.35 -> 0.40 of HBM, the layer backward 715 -> 711 us).
 # DESIGN.md §5 "Agg-free layers" has the A/B.
 AGG_FREE_MIN_ROWS = 1 << 16
+# Encoder1's output BatchNorm + ReLU and compressor[0] as one launch
+# (scgib_enc_out_linear_fwd) where the encoder pair folds compressor[0]; the
+# same bits as scgib_bn_relu_apply + scgib_linear_fwd (False, or
+# SCGIB_ENC_TAIL=0 in the environment at import: the two launches).
+# DESIGN.md §22 has the A/B.
+FUSE_ENC_TAIL = os.environ.get("SCGIB_ENC_TAIL", "1") != "0"
 
 
 # LATE_FORK (always): launch_aside records an event on the current stream now
@@ -663,10 +669,15 @@ class _GinEncoder(torch.autograd.Function):
                                                 *params, readout=readout))
 
     @staticmethod
-    def forward_steps(ctx, h0, graph, gin, training, x, wt, nmap, *params, readout=None):
+    def forward_steps(ctx, h0, graph, gin, training, x, wt, nmap, *params, readout=None,
+                      stop_before_apply=False):
         """forward as a generator that yields after each layer's launch, so
         two encoders on two streams can be enqueued (captured) layer by layer
-        in alternation (_GinEncoderPair); returns forward's result."""
+        in alternation (_GinEncoderPair); returns forward's result.
+
+        stop_before_apply (no readout): everything but the output's BN + ReLU
+        launch; returns (z2, stat, pend) of the last layer for the caller's
+        own consumer (scgib_enc_out_linear_fwd)."""
         pre = x is not None
         if pre:
             x = _f32(x, "gin_encoder x")
@@ -760,9 +771,15 @@ class _GinEncoder(torch.autograd.Function):
                 bn.num_batches_tracked.data_ptr() if track else None,
                 stat.data_ptr(), float(bn.eps), momentum) if defer else None
             yield
-        out = torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
         ro = seg = None
-        if readout is not None:
+        if stop_before_apply and readout is not None:
+            raise _lib.ScgibError("gin_encoder: stop_before_apply with a readout")
+        # (stop_before_apply: the output and its launch are the caller's)
+        out = None if stop_before_apply else \
+            torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
+        if stop_before_apply:
+            pass
+        elif readout is not None:
             ptr, nseg, seg_dims = readout
             ro = torch.empty(nseg, HIDDEN, dtype=torch.float32, device=dev)
             seg = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
@@ -777,6 +794,8 @@ class _GinEncoder(torch.autograd.Function):
         ctx.n_feat = x.shape[1] if pre else None
         ctx.opes = [c._one_plus_eps for c in gin.ginlayers]
         ctx.cnt_key = "gin_bwd"
+        if stop_before_apply:
+            return h, stat_prev, pend
         return out if ro is None else (out, ro)
 
     @staticmethod
@@ -1300,8 +1319,9 @@ class _GinEncoderPair(torch.autograd.Function):
         ego_steps = _GinEncoder.forward_steps(
             ctx.sub[0], None, ego, gin_ego, training, x, wt, nmap, *params[:ne],
             readout=(ego.graph_ptr, ego.batch_size, ego.seg_dims))
+        fuse_tail = ctx.lin and FUSE_ENC_TAIL and core.num_nodes() > 0
         core_steps = _GinEncoder.forward_steps(ctx.sub[1], None, core, gin_core, training, x, wt,
-                                               None, *params[ne:])
+                                               None, *params[ne:], stop_before_apply=fuse_tail)
         with torch.cuda.stream(side):
             s, ro = _drain(ego_steps, "fwd.ego")
             stamp("fwd.ego_end[side]")
@@ -1312,9 +1332,15 @@ class _GinEncoderPair(torch.autograd.Function):
             w0, b0 = _f32(w0, "compressor.0.weight"), _f32(b0, "compressor.0.bias")
             if tuple(w0.shape) != (HIDDEN, HIDDEN):
                 raise _lib.ScgibError("compressor[0] must be Linear(64, 64)")
-            t = torch.empty_like(f)
-            _lib.call("scgib_linear_fwd", _p(f), f.shape[0], _p(w0), _p(b0), _p(t),
-                      _p(core.dims), _stream())
+            if fuse_tail:  # with the output's BN + ReLU: f never read back
+                z2, stat, pend = f
+                f, t = torch.empty_like(z2), torch.empty_like(z2)
+                _lib.call("scgib_enc_out_linear_fwd", _p(z2), _p(stat), z2.shape[0], _p(w0),
+                          _p(b0), _p(f), _p(t), _p(core.dims), _byref(pend), _stream())
+            else:
+                t = torch.empty_like(f)
+                _lib.call("scgib_linear_fwd", _p(f), f.shape[0], _p(w0), _p(b0), _p(t),
+                          _p(core.dims), _stream())
             # (an alias, not the output object itself: ctx -> output -> its
             # grad_fn -> ctx would be a reference cycle that keeps this step's
             # graph, AccumulateGrad nodes included, alive until a gc pass)
