@@ -1219,6 +1219,86 @@ int scgib_adam_step_reduce(const scgib_adam_tensor *tensors, int32_t n_tensors,
                            double beta2, double eps, double weight_decay, uint32_t *counter,
                            scgib_stream_t stream);
 
+/* AdamW by value: the two launches above with decoupled weight decay, the
+ * arithmetic of torch.optim.AdamW(fused=True): p -= lr wd p (in double,
+ * rounded to fp32) before the update, nothing added to g.  (Entry points only,
+ * as everything below in this section: the ABI version stays 24.) */
+int scgib_adamw_step(const scgib_adam_tensor *tensors, int32_t n_tensors, double lr,
+                     double beta1, double beta2, double eps, double weight_decay,
+                     uint32_t *counter, scgib_stream_t stream);
+int scgib_adamw_step_reduce(const scgib_adam_tensor *tensors, int32_t n_tensors,
+                            const scgib_slab_job *jobs, int32_t n_jobs, double lr, double beta1,
+                            double beta2, double eps, double weight_decay, uint32_t *counter,
+                            scgib_stream_t stream);
+
+/* ---- optimizer: hyper-parameters read from the device ------
+ * A captured launch of scgib_adam_step freezes lr / betas / eps / weight_decay
+ * in its graph node.  The _dyn launches read them from a device block that
+ * only host copies write (one scgib_optim_hyper per param group), so a
+ * learning-rate schedule, gradient clipping and the skipping of a non-finite
+ * step run inside a replayed step without a host synchronisation:
+ *   lr_t = lr * factor(c), c = state->calls as the step found it;
+ *   c < warmup: factor = warmup_start + (1 - warmup_start) c / warmup, else
+ *   u = clamp((c - warmup) / max(total - warmup, 1), 0, 1) and factor = 1
+ *   (CONSTANT), 1 - (1 - min_ratio) u (LINEAR), min_ratio + (1 - min_ratio)
+ *   0.5 (1 + cos(pi u)) (COSINE), all in double, by every workgroup for itself.
+ * The blocks are 8-byte aligned and zeroed before their first use. */
+enum { SCGIB_SCHED_CONSTANT = 0, SCGIB_SCHED_LINEAR = 1, SCGIB_SCHED_COSINE = 2 };
+typedef struct {
+    double lr, beta1, beta2, eps, weight_decay;
+    double warmup_start, min_ratio;
+    double max_grad_norm; /* < 0: no clipping (coef = 1); read by scgib_grad_norm */
+    int64_t warmup, total;
+    int32_t kind;         /* SCGIB_SCHED_* */
+    int32_t pad_;
+} scgib_optim_hyper;      /* 88 bytes */
+typedef struct {
+    double sumsq;         /* S = sum (double)g (double)g of the step's gradients */
+    float norm;           /* (float)sqrt(S), before clipping */
+    float coef;           /* min(1, max_grad_norm / (norm + 1e-6f)), fp32 (NaN stays NaN) */
+    int32_t finite;       /* isfinite(norm) */
+    int32_t pad_;
+    int64_t calls;        /* steps taken, skipped ones included */
+    int64_t skipped;
+} scgib_optim_state;      /* 40 bytes */
+enum {
+    SCGIB_OPTIM_NORM = 1,    /* a scgib_grad_norm preceded: use g * state->coef */
+    SCGIB_OPTIM_SKIP = 2,    /* with _NORM: state->finite == 0 changes no tensor */
+    SCGIB_OPTIM_ADVANCE = 4  /* the step's last launch: calls (and skipped) advance */
+};
+/* scgib_grad_norm: the global L2 norm of the table's gradients in a fixed
+ * order (1024-element chunks, a fixed tree per workgroup, the chunk partials
+ * added by the last workgroup to arrive in an order that depends on their
+ * number alone): bitwise reproducible, no floating-point atomics.  ws:
+ * scgib_grad_norm_ws_doubles(scgib_grad_norm_chunks(tensors, n)) doubles,
+ * written before they are read; counter: one uint32, zero on entry, left zero.
+ * More than scgib_adam_max_tensors() tensors take several launches: first != 0
+ * on the first starts state->sumsq, each adds its total in launch order,
+ * last != 0 on the last writes norm, coef and finite.  hyper: the block whose
+ * max_grad_norm applies (the norm is global: group 0's).  Only .grad and
+ * .numel (and the validity of the other fields) of the table matter. */
+int64_t scgib_grad_norm_chunks(const scgib_adam_tensor *tensors, int32_t n_tensors);
+int64_t scgib_grad_norm_ws_doubles(int64_t n_chunks);
+int scgib_grad_norm(const scgib_adam_tensor *tensors, int32_t n_tensors, double *ws,
+                    uint32_t *counter, const scgib_optim_hyper *hyper, scgib_optim_state *state,
+                    int32_t first, int32_t last, scgib_stream_t stream);
+/* scgib_adam_step / _step_reduce with the hyper-parameters of `hyper` (this
+ * launch's param group), the same adam_elem / adam_coef.  flags: SCGIB_OPTIM_*;
+ * decoupled != 0: AdamW.  The last workgroup writes *last_lr = lr_t and, with
+ * SCGIB_OPTIM_ADVANCE, advances state->calls (and ->skipped on a skip); on a
+ * skip no parameter, moment or tensor step changes.  n_tensors = 0 with
+ * _ADVANCE still counts the call.  The fused reduce has no norm launch before
+ * it: _NORM / _SKIP there are SCGIB_EINVAL. */
+int scgib_adam_step_dyn(const scgib_adam_tensor *tensors, int32_t n_tensors,
+                        const scgib_optim_hyper *hyper, scgib_optim_state *state,
+                        double *last_lr, int32_t flags, int32_t decoupled, uint32_t *counter,
+                        scgib_stream_t stream);
+int scgib_adam_step_reduce_dyn(const scgib_adam_tensor *tensors, int32_t n_tensors,
+                               const scgib_slab_job *jobs, int32_t n_jobs,
+                               const scgib_optim_hyper *hyper, scgib_optim_state *state,
+                               double *last_lr, int32_t flags, int32_t decoupled,
+                               uint32_t *counter, scgib_stream_t stream);
+
 
 /* ---- data parallelism: gradient bucket (dist.GradAllReducer) --------------
  * scgib_grad_pack: flat[offset + i] = data[i] for every slice, one launch;

@@ -211,6 +211,14 @@ SIGNATURES = {
     "scgib_adam_step": (ctypes.c_int, [_P, _I32, _D, _D, _D, _D, _D, _P, _P]),
     "scgib_adam_reduce_max_jobs": (_I64, []),
     "scgib_adam_step_reduce": (ctypes.c_int, [_P, _I32, _P, _I32, _D, _D, _D, _D, _D, _P, _P]),
+    "scgib_adamw_step": (ctypes.c_int, [_P, _I32, _D, _D, _D, _D, _D, _P, _P]),
+    "scgib_adamw_step_reduce": (ctypes.c_int, [_P, _I32, _P, _I32, _D, _D, _D, _D, _D, _P, _P]),
+    "scgib_grad_norm_chunks": (_I64, [_P, _I32]),
+    "scgib_grad_norm_ws_doubles": (_I64, [_I64]),
+    "scgib_grad_norm": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _I32, _P]),
+    "scgib_adam_step_dyn": (ctypes.c_int, [_P, _I32, _P, _P, _P, _I32, _I32, _P, _P]),
+    "scgib_adam_step_reduce_dyn": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _P,
+                                                  _P]),
     "scgib_eval_tiles": (_I64, [_I64]),
     "scgib_eval_append": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I64, _P, _P]),
     "scgib_eval_keys": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
@@ -248,6 +256,23 @@ class AdamTensor(ctypes.Structure):
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p),
                 ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
                 ("step", ctypes.c_void_p), ("numel", ctypes.c_int64)]
+
+
+class OptimHyper(ctypes.Structure):
+    """scgib_optim_hyper (include/scgib.h)."""
+    _fields_ = ([(n, ctypes.c_double) for n in
+                 ("lr", "beta1", "beta2", "eps", "weight_decay", "warmup_start", "min_ratio",
+                  "max_grad_norm")] +
+                [("warmup", ctypes.c_int64), ("total", ctypes.c_int64),
+                 ("kind", ctypes.c_int32), ("pad_", ctypes.c_int32)])
+
+
+# scgib_optim_state (include/scgib.h) as 8-byte words: sumsq | norm, coef |
+# finite, pad | calls | skipped
+OPTIM_STATE_WORDS = 5
+OPTIM_NORM, OPTIM_SKIP, OPTIM_ADVANCE = 1, 2, 4
+SCHED_KINDS = {"constant": 0, "linear": 1, "cosine": 2}
+
 
 class SlabJob(ctypes.Structure):
     """scgib_slab_job (include/scgib.h)."""
