@@ -9,6 +9,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+import typing
 import weakref
 
 import numpy as np
@@ -118,16 +119,24 @@ _PENDING_RU = [None]
 DEFER_LOSS_REDUCE = True
 
 
+class SlabWork(typing.NamedTuple):
+    """One slab-reduce job and the tensors (its slab, an output nothing else
+    references yet) that must stay allocated until its reduce is enqueued: a
+    job handed on, folded or dropped takes its buffers with it."""
+    job: _lib.SlabJob
+    owns: tuple
+
+
 class SlabScope:
-    """Slab-reduce jobs collected between an encoder pair's forward and its
-    backward (which drains them into a chain's final reduce)."""
+    """Slab-reduce work collected between an encoder pair's forward and its
+    backward (which drains it into a chain's final reduce)."""
 
     _live = weakref.WeakSet()
     # the deferred gradients live on the HIP device (a hook for the host tests)
     _device_ok = staticmethod(lambda p: p.is_cuda)
 
     def __init__(self):
-        self.jobs, self.keep, self.later = [], [], []
+        self.work, self.later = [], []
         self.open, self.ok, self.callback, self.stream = True, True, False, None
         # parameters of the loss-section nodes that asked for this scope, and
         # those two nodes share: autograd sums such a pair's gradients at once,
@@ -156,8 +165,8 @@ class SlabScope:
             for p in params)
 
     def add(self, slab, wgrad, width, n_slabs):
-        self.jobs.append(_lib.SlabJob(slab.data_ptr(), wgrad.data_ptr(), width, n_slabs, 0))
-        self.keep += [slab, wgrad]
+        self.work.append(SlabWork(_lib.SlabJob(slab.data_ptr(), wgrad.data_ptr(), width,
+                                               n_slabs, 0), (slab, wgrad)))
         self._arm(slab)
 
     def defer(self, launch, *tensors):
@@ -181,16 +190,15 @@ class SlabScope:
                 pass
 
     def _flush(self):
-        if not self.open or not (self.jobs or self.later):
+        if not self.open or not (self.work or self.later):
             return
-        later = self.take_later()
-        jobs, keep = self.take()
+        later, work = self.take_later(), self.take()
         with torch.cuda.stream(self.stream):
             for launch, _ in later:
                 launch()
-            if jobs:
-                _reduce_jobs(jobs, _stream())
-        del keep, later  # the slabs stay allocated until the launches are enqueued
+            if work:
+                _reduce_work(work, _stream())
+        del work, later  # the slabs stay allocated until the launches are enqueued
 
     def take_later(self):
         later, self.later = self.later, []
@@ -198,9 +206,8 @@ class SlabScope:
 
     def take(self):
         self.open = False
-        jobs, keep = self.jobs, self.keep
-        self.jobs, self.keep = [], []
-        return jobs, keep
+        work, self.work = self.work, []
+        return work
 
 
 _SLAB_SCOPE = [None]  # the latest encoder pair's scope (captured by later loss ops)
@@ -405,18 +412,18 @@ def _gin_layer_params(gin):
     return out
 
 
-def _drain(gen, tag=None):
-    """Run a step generator to completion and return its value (``tag``:
-    stamps at each of its yields, at stamp level 2)."""
-    i = 0
-    while True:
-        try:
-            next(gen)
-        except StopIteration as stop:
-            return stop.value
-        if tag is not None and _STAMPS["level"] >= 2:
-            stamp(f"{tag}.{i}")
-        i += 1
+def _layer_stamp(tag, i):
+    """The stamp after the ``i``-th layer a GIN chain enqueues (stamp level 2)."""
+    if tag is not None and _STAMPS["level"] >= 2:
+        stamp(f"{tag}.{i}")
+
+
+def _check_transfer_fold(x, transfer):
+    """What folding transfer_d into a GIN layer 0 needs of it and its input."""
+    if transfer.bias is not None or transfer.weight.shape != (32, x.shape[1]) or x.shape[1] > 16:
+        raise _lib.ScgibError("transfer_d fold needs Linear(F <= 16, 32, bias=False)")
+    if x.requires_grad:
+        raise _lib.ScgibError("transfer_d fold: no gradient w.r.t. the raw features")
 
 
 # ---------------------------------------------------------------------------
@@ -622,7 +629,7 @@ FUSE_FINAL_ADAM = True
 # (profiles/r06_noise/fuse_adam_ab.txt, fuse_ept_ab.txt)
 FUSE_FINAL_MIN_SLABS = 0
 _FINAL_ARMED = [False]
-_FINAL_PENDING = {}  # device index -> [(jobs, keep)]
+_FINAL_PENDING = {}  # device index -> [[SlabWork]], one list per pending backward
 
 
 @contextlib.contextmanager
@@ -634,8 +641,7 @@ def fuse_final_into_step():
     finally:
         _FINAL_ARMED[0] = prev
         for idx in list(_FINAL_PENDING):
-            for jobs, _keep in _FINAL_PENDING.pop(idx):
-                _reduce_jobs(jobs, _stream())
+            reduce_pending(_FINAL_PENDING.pop(idx))
 
 
 def take_final(device):
@@ -652,6 +658,18 @@ def _reduce_jobs(jobs, st, max_wg=0):
                   int(max_wg), st)
 
 
+def _reduce_work(work, st):
+    """One fixed-order reduce launch over a list of SlabWork (none if empty)."""
+    if work:
+        _reduce_jobs([w.job for w in work], st)
+
+
+def reduce_pending(pending):
+    """One reduce launch per pending backward (a list of SlabWork each)."""
+    for work in pending:
+        _reduce_work(work, _stream())
+
+
 class _GinEncoder(torch.autograd.Function):
     """GIN.forward (models.py:66-72) as fused HIP layers; see gin_layer.hip.
 
@@ -661,23 +679,17 @@ class _GinEncoder(torch.autograd.Function):
     never materialised — and d Wt comes out of the layer-0 backward."""
 
     @staticmethod
-    def forward(ctx, h0, graph, gin, training, x, wt, nmap, *params, readout=None):
-        """readout = (ptr, nseg, seg_dims): also return the segment sums of
-        the output (dgl.sum_nodes, fused with the last BN + ReLU); the backward
-        then takes (g_out, g_readout)."""
-        return _drain(_GinEncoder.forward_steps(ctx, h0, graph, gin, training, x, wt, nmap,
-                                                *params, readout=readout))
-
-    @staticmethod
-    def forward_steps(ctx, h0, graph, gin, training, x, wt, nmap, *params, readout=None,
-                      stop_before_apply=False):
-        """forward as a generator that yields after each layer's launch, so
-        two encoders on two streams can be enqueued (captured) layer by layer
-        in alternation (_GinEncoderPair); returns forward's result.
-
+    def forward(ctx, h0, graph, gin, training, x, wt, nmap, *params, readout=None,
+                stop_before_apply=False, stamp_tag=None):
+        """Keywords: direct calls only (_GinEncoderPair, on stand-in contexts).
+        readout = (ptr, nseg, seg_dims): also return the segment sums of the
+        output (dgl.sum_nodes, fused with the last BN + ReLU); the backward then
+        takes (g_out, g_readout).  stamp_tag: a level-2 stamp after each layer.
         stop_before_apply (no readout): everything but the output's BN + ReLU
         launch; returns (z2, stat, pend) of the last layer for the caller's
         own consumer (scgib_enc_out_linear_fwd)."""
+        if stop_before_apply and readout is not None:
+            raise _lib.ScgibError("gin_encoder: stop_before_apply with a readout")
         pre = x is not None
         if pre:
             x = _f32(x, "gin_encoder x")
@@ -770,24 +782,20 @@ class _GinEncoder(torch.autograd.Function):
                 bn.running_var.data_ptr() if track else None,
                 bn.num_batches_tracked.data_ptr() if track else None,
                 stat.data_ptr(), float(bn.eps), momentum) if defer else None
-            yield
-        ro = seg = None
-        if stop_before_apply and readout is not None:
-            raise _lib.ScgibError("gin_encoder: stop_before_apply with a readout")
-        # (stop_before_apply: the output and its launch are the caller's)
-        out = None if stop_before_apply else \
-            torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
-        if stop_before_apply:
-            pass
-        elif readout is not None:
-            ptr, nseg, seg_dims = readout
-            ro = torch.empty(nseg, HIDDEN, dtype=torch.float32, device=dev)
-            seg = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-            _lib.call("scgib_bn_relu_segment_sum", _p(h), _p(stat_prev), _p(ptr), nseg, n,
-                      _p(out), _p(ro), _p(seg), _p(seg_dims), _p(graph.dims), _byref(pend), st)
-        else:
-            _lib.call("scgib_bn_relu_apply", _p(h), _p(stat_prev), n, _p(out), _p(graph.dims),
-                      _byref(pend), st)
+            _layer_stamp(stamp_tag, l)
+        out = ro = seg = None
+        if not stop_before_apply:  # (else the output and its launch are the caller's)
+            out = torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
+            if readout is not None:
+                ptr, nseg, seg_dims = readout
+                ro = torch.empty(nseg, HIDDEN, dtype=torch.float32, device=dev)
+                seg = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+                _lib.call("scgib_bn_relu_segment_sum", _p(h), _p(stat_prev), _p(ptr), nseg, n,
+                          _p(out), _p(ro), _p(seg), _p(seg_dims), _p(graph.dims), _byref(pend),
+                          st)
+            else:
+                _lib.call("scgib_bn_relu_apply", _p(h), _p(stat_prev), n, _p(out),
+                          _p(graph.dims), _byref(pend), st)
         ctx.seg = seg
         ctx.save_for_backward(*saved, *params, *( (aggx,) if pre else ()))
         ctx.graph, ctx.L, ctx.training, ctx.pre = graph, L, training, pre
@@ -800,259 +808,289 @@ class _GinEncoder(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_readout=None):
-        if not isinstance(ctx, _Ctx):  # (the encoder pair sets its sub-contexts' own)
-            ctx.need = ctx.needs_input_grad[7:]
-        return _drain(_GinEncoder.backward_steps(ctx, g_out, g_readout),
-                      getattr(ctx, "stamp_tag", None))
+        return _GinBackward(ctx, _ChainLinks(need=ctx.needs_input_grad[7:]), g_out,
+                            g_readout).run()
 
-    @staticmethod
-    def backward_steps(ctx, g_out, g_readout=None):
-        """backward as a generator (yields after each layer), see forward_steps."""
-        L, gr, pre = ctx.L, ctx.graph, ctx.pre
+
+class _ChainLinks:
+    """What the caller of a GIN chain's backward (_GinBackward) hands it and
+    takes back: _GinEncoderPair steers its two chains with one each, a
+    stand-alone encoder passes the defaults.  Inputs:
+      need           which of the 6 L parameters take a gradient (None: all).
+                     The fine-tune freezing quirk (models.py:424-434) leaves
+                     most layers frozen: a layer none of whose W1 / b1 / W2 / b2
+                     does runs without the weight products (need_w = 0; the
+                     same data gradients, bitwise)
+      stamp_tag      label of the level-2 stamps, one after each layer
+      first_fold     a SlabWork for the extra workgroups of the chain's first
+                     statistics launch (a chain with a readout gradient has
+                     none: the work then joins the final reduce)
+      extra          SlabWork for the chain's final reduce launch
+      spare_dwt_row  (fold chains) one more layer-0 slab row, whose d Wt columns
+                     another chain's reduce fills: this chain's final reduce
+                     then returns the sum of both
+      dwt_into       (fold chains) where d Wt is reduced into — such a spare
+                     row — instead of a tensor of the chain's own
+      defer_final    leave the final reduce in ``final`` instead of launching it
+    Outputs: dwt_row_ptr, dwt_row_slab (the spare row's d Wt columns and the
+    slab they are in) and final (the deferred reduce's SlabWork; None: none)."""
+
+    __slots__ = ("need", "stamp_tag", "first_fold", "extra", "spare_dwt_row", "dwt_into",
+                 "defer_final", "dwt_row_ptr", "dwt_row_slab", "final")
+
+    def __init__(self, need=None, stamp_tag=None, first_fold=None, extra=(),
+                 spare_dwt_row=False, dwt_into=None, defer_final=False):
+        self.need, self.stamp_tag, self.first_fold, self.extra = need, stamp_tag, first_fold, extra
+        self.spare_dwt_row, self.dwt_into, self.defer_final = spare_dwt_row, dwt_into, defer_final
+        self.dwt_row_ptr = self.dwt_row_slab = self.final = None
+
+
+def _mlp2_grad_views(wg, d_in):
+    """(dW1, db1, dW2, db2) as views of a weight-gradient row laid out
+    dW2 [64][64] | dW1 [64][d_in] | db2 | db1 (the GIN layers and the MLP heads)."""
+    o, o1 = HIDDEN * HIDDEN, HIDDEN * HIDDEN + HIDDEN * d_in
+    return (wg[o:o1].view(HIDDEN, d_in), wg[o1 + HIDDEN:o1 + 2 * HIDDEN],
+            wg[:o].view(HIDDEN, HIDDEN), wg[o1:o1 + HIDDEN])
+
+
+def _z_grad_views(wg):
+    """(dW1, db1, dW2, db2) as views of an agg-free layer's weight-gradient
+    row: dW2 | db2 | db1 (_Z_SLAB floats) and then dW1 (at _Z_W1_OFF)."""
+    o = HIDDEN * HIDDEN
+    return (wg[_Z_W1_OFF:].view(HIDDEN, HIDDEN), wg[o + HIDDEN:_Z_SLAB],
+            wg[:o].view(HIDDEN, HIDDEN), wg[o:o + HIDDEN])
+
+
+def _job_ref(work):  # by-reference argument for one SlabWork's job (None: NULL)
+    return _byref(work.job if work is not None else None)
+
+
+class _GinBackward:
+    """One pass down a GIN chain's backward: per layer a statistics launch
+    (stats) and the layer launch of its kind (layer_z, layer0, layer_plain).
+    What a layer leaves for the one below and the buffers still being read are
+    attributes, each dropped at a fixed point of the pass: a captured step
+    reuses the allocator's blocks in that order."""
+
+    def __init__(self, ctx, links, g_out, g_readout=None):
+        L = ctx.L
         t = ctx.saved_tensors
-        saved, params = t[: 4 * L], t[4 * L: 4 * L + 6 * L]
-        aggx = t[-1] if pre else None
+        self.ctx, self.links = ctx, links
+        self.saved, self.params = t[: 4 * L], t[4 * L: 4 * L + 6 * L]
+        self.aggx = t[-1] if ctx.pre else None
         if g_readout is not None and ctx.seg is None:
             raise _lib.ScgibError("gin_encoder.backward: readout gradient without a readout")
+        if not ctx.pre and (links.spare_dwt_row or links.dwt_into is not None):
+            raise _lib.ScgibError("gin_encoder.backward: d Wt links on a chain without the fold")
         if g_out is not None:
             g_out = _f32(g_out, "gin_encoder.backward")
         elif g_readout is None:  # the output is unused
-            g_out = torch.zeros_like(saved[2])
+            g_out = torch.zeros_like(self.saved[2])
         if g_readout is not None:
             g_readout = _f32(g_readout, "gin_encoder.backward readout")
-        n = saved[2].shape[0]
-        dev = saved[2].device
-        st = _stream()
-        bn_ws = torch.empty(int(_lib.query("scgib_gin_bn_ws_floats", n)), dtype=torch.float32,
-                            device=dev)
-        cnt = scan_state(dev, ctx.cnt_key, int(_lib.query("scgib_gin_counters", n)))
+        self.g_out, self.g_readout = g_out, g_readout
+        self.n, self.dev = n, dev = self.saved[2].shape[0], self.saved[2].device
+        self.st = _stream()
+        self.bn_ws = torch.empty(int(_lib.query("scgib_gin_bn_ws_floats", n)),
+                                 dtype=torch.float32, device=dev)
+        self.cnt = scan_state(dev, ctx.cnt_key, int(_lib.query("scgib_gin_counters", n)))
         # deferred BN-backward finalize: each layer's gin_bwd_k finishes the sums
-        defer = int(DEFER_BN and n <= int(_lib.query("scgib_gin_defer_max_nodes")))
-        gpart = bn_ws.data_ptr() + 4 * int(_lib.query("scgib_gin_bn_gpart_offset", n))
-        grads = [None] * (6 * L)
-        # which parameters take a gradient (the fine-tune freezing quirk,
-        # models.py:424-434, leaves most GIN layers frozen): a layer none of
-        # whose W1 / b1 / W2 / b2 does runs its backward without the weight
-        # products (scgib_gin_layer_bwd need_w = 0; same data gradients, bitwise)
-        need = getattr(ctx, "need", None)
-        dagg_next, dwt = None, None
-        # an agg-free layer l + 1 hands layer l's statistics launch its dz1,
-        # W1 and the row of its weight gradient dW1 lands in
-        dz1_next = w1_next = wgrad_next = None  # (wgrad_next None: layer l + 1 is frozen)
+        self.defer = int(DEFER_BN and n <= int(_lib.query("scgib_gin_defer_max_nodes")))
+        self.gpart = self.bn_ws.data_ptr() + 4 * int(_lib.query("scgib_gin_bn_gpart_offset", n))
+        self.dy = self.bn_g = self.coef = self.dagg = self.dwt = None
+        # layer l + 1 hands layer l's statistics launch its d(agg), or (agg-free)
+        # its dz1, W1 and the row dW1 lands in (wgrad_next None: l + 1 is frozen)
+        self.dagg_next = self.dz1_next = self.w1_next = self.wgrad_next = None
+        # pend: SlabWork for the next statistics launch's extra workgroups (one
+        # for scgib_gin_bwd_stats_bn_fold, two for scgib_gin_bwd_stats_z); its
+        # slabs are released once that launch is enqueued (the allocator may then
+        # reuse the blocks for later tensors of this stream).  final: the rest
+        self.pend, self.final = [], []
+        self.w1_fold = None  # the dW1 partials for the agg-free layer backward next
+
+    def _take_fold(self):
+        return self.pend.pop(0) if self.pend else None
+
+    def stats(self, l, z2, stat, agg_free):
+        """dy, the tile sums and the BN-backward finalize of layer ``l`` in
+        one launch; which one depends on what came down from above."""
+        ctx, links, gr, n, dev, st = self.ctx, self.links, self.ctx.graph, self.n, self.dev, self.st
+        # (the previous layer's dy is read by nothing not yet enqueued: released
+        # before the new allocations, whose blocks the captured step can then reuse)
+        self.dy = None
+        self.dy = dy = torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
+        self.bn_g = bn_g = torch.empty(2, HIDDEN, dtype=torch.float32, device=dev)  # dgamma, dbeta
+        self.coef = coef = torch.empty(2, HIDDEN, dtype=torch.float32, device=dev)
+        tail = (_p(z2), _p(stat), n, int(ctx.training), _p(dy), _p(bn_g[0]), _p(bn_g[1]),
+                _p(coef), _p(self.bn_ws), _p(self.cnt), _p(gr.dims), self.defer)
+        meta = {"n": n, "e": gr.edge_capacity(), "d_in": HIDDEN}
+        if self.dz1_next is not None:
+            # layer l + 1 is agg-free: gather its dz1, d h_l = g W1_{l+1},
+            # and dW1_{l+1} = g^T h_l as per-workgroup partials
+            nz = int(_lib.query("scgib_gin_bwd_stats_z_slabs", n))
+            wgn = self.wgrad_next is not None
+            wslab = torch.empty(nz * HIDDEN * HIDDEN, dtype=torch.float32,
+                                device=dev) if wgn else None
+            # (no folds when the walk fills the chip's two slots per CU: the
+            # extra workgroups would wait for a second wave; the pending work
+            # then goes to the next agg-free layer backward, or the final reduce)
+            room = 2 * 256 - nz
+            folds = []
+            while self.pend and room >= (self.pend[0].job.width + 63) // 64:
+                room -= (self.pend[0].job.width + 63) // 64
+                folds.append(self.pend.pop(0))
+            table = (_lib.SlabJob * max(len(folds), 1))(*[w.job for w in folds])
+            _launch("scgib_gin_bwd_stats_z", {**meta, "z": True, "wg": wgn},
+                    _p(self.dz1_next), _p(gr.rowptr_t), _p(gr.col_t), ctx.opes[l + 1],
+                    _p(self.w1_next), *tail, _p(wslab), int(wgn),
+                    ctypes.cast(table, ctypes.c_void_p), len(folds), st)
+            if wgn:  # dW1_{l+1} lands after its dW2 | db2 | db1 (wgrad_next's layout)
+                work = SlabWork(_lib.SlabJob(wslab.data_ptr(),
+                                             self.wgrad_next.data_ptr() + 4 * _Z_W1_OFF,
+                                             HIDDEN * HIDDEN, nz, 0), (wslab,))
+                # (one partial per walking workgroup — per tile at small batches:
+                # reduced by this layer's agg-free backward, the next launch,
+                # whose grid leaves room; else with the chain's final reduce)
+                if FOLD_SLABS and agg_free:
+                    self.w1_fold = work
+                else:
+                    self.final.append(work)
+            self.dz1_next = self.w1_next = self.wgrad_next = None
+        elif self.dagg_next is not None:
+            fold = self._take_fold()
+            _launch("scgib_gin_bwd_stats_bn_fold", meta, _p(self.dagg_next), _p(gr.rowptr_t),
+                    _p(gr.col_t), ctx.opes[l + 1], *tail, _job_ref(fold), st)
+            self.dagg_next = None
+        elif self.g_readout is not None:
+            # the readout's broadcast backward folded into the last layer
+            _launch("scgib_gin_bwd_stats_seg_bn", {**meta, "e": 0}, _p(self.g_out),
+                    _p(self.g_readout), _p(ctx.seg), *tail, st)
+        else:
+            # (first_fold: a loss-section SlabWork handed over by the encoder
+            # pair — reduced in extra workgroups here, its slab then released)
+            fold, links.first_fold = links.first_fold, None
+            _launch("scgib_gin_bwd_stats_bn_fold", {**meta, "e": 0}, _p(self.g_out), None, None,
+                    1.0, *tail, _job_ref(fold), st)
+
+    def layer_z(self, lay, meta, wg, bpend):
+        """An agg-free layer: dz1 out, dW2 | db2 | db1 here, dW1 from layer
+        l - 1's statistics launch (always one: l >= 1); frozen (not wg): the
+        same dz1 chain, no weight products.  Returns (gradient views, work)."""
+        agg, r, z2, stat, w1c, b1c, w2c = lay
+        n, dev = self.n, self.dev
+        meta["z"] = True
+        nsz = int(_lib.query("scgib_gin_layer_bwd_z_slabs", n))
+        slab = torch.empty(nsz * _Z_SLAB, dtype=torch.float32, device=dev) if wg else None
+        dz1 = torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
+        f2 = self._take_fold()  # the previous agg-free layer's dW2 | db slab
+        _launch("scgib_gin_layer_bwd_z", meta, _p(self.dy), _p(z2), _p(r), _p(stat),
+                _p(self.coef), _p(w2c), n, _p(dz1), _p(slab), int(wg), _p(self.ctx.graph.dims),
+                _byref(bpend), _job_ref(self.w1_fold), _job_ref(f2), self.st)
+        self.w1_fold = f2 = None
+        views, work, wgrad = None, [], None
+        if wg:
+            wgrad = torch.empty(_Z_SLAB + HIDDEN * HIDDEN, dtype=torch.float32, device=dev)
+            work = [SlabWork(_lib.SlabJob(slab.data_ptr(), wgrad.data_ptr(), _Z_SLAB, nsz, 0),
+                             (slab,))]
+            views = _z_grad_views(wgrad)
+        self.dz1_next, self.w1_next, self.wgrad_next = dz1, w1c, wgrad
+        return views, work
+
+    def layer0(self, lay, meta, wg, bpend):
+        """Layer 0 with transfer_d folded: no d(agg) out, d Wt = the tail of
+        its slab rows.  Frozen (not wg): no weight products, only d Wt."""
+        agg, r, z2, stat, w1c, b1c, w2c = lay
+        ctx, links, n, dev = self.ctx, self.links, self.n, self.dev
         nslab = int(_lib.query("scgib_gin_bwd_slabs", n))
-        jobs, keep = [], []
-        # slab jobs waiting to be reduced by the next statistics launch's extra
-        # workgroups (one for scgib_gin_bwd_stats_bn_fold, two for
-        # scgib_gin_bwd_stats_z), with their slabs: released once that launch
-        # is enqueued (the allocator may then reuse the blocks for later
-        # tensors of this stream); whatever is left goes to the final reduce
-        pend_jobs = []
-        w1_fold = None  # the dW1 partials job for the agg-free layer backward next
+        width = int(_lib.query("scgib_gin_layer0_slab_width"))
+        xrow = int(links.spare_dwt_row)
+        slab = torch.empty((nslab + xrow) * width, dtype=torch.float32, device=dev)
+        _launch("scgib_gin_layer0_bwd", meta, _p(self.dy), _p(z2), _p(r), _p(agg), _p(self.aggx),
+                ctx.n_feat, _p(stat), _p(self.coef), _p(w1c), _p(b1c), _p(w2c), n, _p(slab),
+                int(wg), _p(ctx.graph.dims), _byref(bpend), self.st)
+        self.dagg = None
+        o, nwt = HIDDEN * HIDDEN + HIDDEN * agg.shape[1] + 2 * HIDDEN, 32 * ctx.n_feat
+        wgrad = torch.empty(width, dtype=torch.float32, device=dev) if wg else None
+        into = links.dwt_into
+        # d Wt as a job of its own: alone (frozen), into another chain's row,
+        # or over the spare row as well
+        split, work = not wg or into is not None or xrow, []
+        if into is None:  # d Wt occupies 32 * F of the row's 512 last columns
+            dwt = wgrad[o:o + nwt] if wg else torch.empty(nwt, dtype=torch.float32, device=dev)
+            into, self.dwt = dwt.data_ptr(), dwt.view(32, ctx.n_feat)
+        if wg:
+            work.append(SlabWork(_lib.SlabJob(slab.data_ptr(), wgrad.data_ptr(),
+                                              o if split else o + nwt, nslab, width), (slab,)))
+        if split:
+            work.append(SlabWork(_lib.SlabJob(slab.data_ptr() + 4 * o, into, nwt, nslab + xrow,
+                                              width), (slab,)))
+        if xrow:
+            links.dwt_row_ptr = slab.data_ptr() + 4 * (nslab * width + o)
+            links.dwt_row_slab = slab
+        return (_mlp2_grad_views(wgrad, agg.shape[1]) if wg else None), work
 
-        def take_folds(k):
-            got = pend_jobs[:k]
-            del pend_jobs[:k]
-            return got
+    def layer_plain(self, lay, meta, wg, bpend):
+        """A stored-agg layer: d(agg) out for the statistics launch below."""
+        agg, r, z2, stat, w1c, b1c, w2c = lay
+        n, dev, d_in = self.n, self.dev, agg.shape[1]
+        width = HIDDEN * HIDDEN + HIDDEN * d_in + 2 * HIDDEN
+        slab = torch.empty(int(_lib.query("scgib_gin_slab_floats", n, d_in)),
+                           dtype=torch.float32, device=dev) if wg else None
+        self.dagg = dagg = torch.empty(n, d_in, dtype=torch.float32, device=dev)
+        _launch("scgib_gin_layer_bwd", meta, _p(self.dy), _p(z2), _p(r), _p(agg), d_in, _p(stat),
+                _p(self.coef), _p(w1c), _p(b1c), _p(w2c), n, _p(dagg), _p(slab), _NULL, int(wg),
+                _p(self.ctx.graph.dims), _byref(bpend), self.st)
+        self.dagg_next = dagg
+        if not wg:
+            return None, []
+        wgrad = torch.empty(width, dtype=torch.float32, device=dev)
+        ns = int(_lib.query("scgib_gin_layer_bwd_slabs", n, d_in))
+        return _mlp2_grad_views(wgrad, d_in), [
+            SlabWork(_lib.SlabJob(slab.data_ptr(), wgrad.data_ptr(), width, ns, 0), (slab,))]
 
+    def run(self):
+        ctx, links, gr = self.ctx, self.links, self.ctx.graph
+        L, pre, need = ctx.L, ctx.pre, links.need
+        grads = [None] * (6 * L)
         for l in reversed(range(L)):
-            agg, r, z2, stat = saved[4 * l: 4 * l + 4]  # r None: recomputed by the kernel
-            w1, b1, w2 = params[6 * l], params[6 * l + 1], params[6 * l + 2]
+            agg, r, z2, stat = self.saved[4 * l: 4 * l + 4]  # r None: recomputed by the kernel
+            w1, b1, w2 = self.params[6 * l: 6 * l + 3]
             d_in = agg.shape[1] if agg is not None else HIDDEN  # (agg None: an agg-free layer)
-            # (the previous layer's dy and slab are no longer read by anything
-            # not yet enqueued: released before the new allocations, whose
-            # blocks the captured step can then reuse)
-            dy = slab = None
-            dy = torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
-            bn_g = torch.empty(2, HIDDEN, dtype=torch.float32, device=dev)  # dgamma, dbeta
-            coef = torch.empty(2, HIDDEN, dtype=torch.float32, device=dev)
-            # dy, tile sums and the BN-backward finalize in one launch
-            if dagg_next is None and dz1_next is None and g_readout is not None:
-                # the readout's broadcast backward folded into the last layer
-                _launch("scgib_gin_bwd_stats_seg_bn", {"n": n, "e": 0, "d_in": HIDDEN}, _p(g_out), _p(g_readout),
-                        _p(ctx.seg), _p(z2), _p(stat), n, int(ctx.training), _p(dy),
-                        _p(bn_g[0]), _p(bn_g[1]), _p(coef), _p(bn_ws), _p(cnt), _p(gr.dims),
-                        defer, st)
-            elif dagg_next is None and dz1_next is None:
-                # (first_fold: a loss-section slab job handed over by the encoder
-                # pair — reduced in extra workgroups here, its slab then released)
-                ff = getattr(ctx, "first_fold", None)
-                ctx.first_fold = None
-                _launch("scgib_gin_bwd_stats_bn_fold", {"n": n, "e": 0, "d_in": HIDDEN}, _p(g_out),
-                        None, None, 1.0, _p(z2), _p(stat), n, int(ctx.training), _p(dy),
-                        _p(bn_g[0]), _p(bn_g[1]), _p(coef), _p(bn_ws), _p(cnt), _p(gr.dims),
-                        defer, _byref(ff[0] if ff else None), st)
-                ff = None
-            elif dz1_next is not None:
-                # layer l + 1 is agg-free: gather its dz1, d h_l = g W1_{l+1},
-                # and dW1_{l+1} = g^T h_l as per-workgroup partials
-                nz = int(_lib.query("scgib_gin_bwd_stats_z_slabs", n))
-                wgn = wgrad_next is not None
-                wslab = torch.empty(nz * HIDDEN * HIDDEN, dtype=torch.float32,
-                                    device=dev) if wgn else None
-                # (no folds when the walk fills the chip's two slots per CU: the
-                # extra workgroups would wait for a second wave; the pending jobs
-                # then go to the next agg-free layer backward, or the final reduce)
-                room = 2 * 256 - nz
-                folds = []
-                while pend_jobs and room >= (pend_jobs[0][0].width + 63) // 64:
-                    room -= (pend_jobs[0][0].width + 63) // 64
-                    folds += take_folds(1)
-                table = (_lib.SlabJob * max(len(folds), 1))(*[j for j, _ in folds])
-                _launch("scgib_gin_bwd_stats_z", {"n": n, "e": gr.edge_capacity(), "d_in": HIDDEN,
-                                                  "z": True, "wg": wgn},
-                        _p(dz1_next), _p(gr.rowptr_t), _p(gr.col_t), ctx.opes[l + 1],
-                        _p(w1_next), _p(z2), _p(stat), n, int(ctx.training), _p(dy), _p(bn_g[0]),
-                        _p(bn_g[1]), _p(coef), _p(bn_ws), _p(cnt), _p(gr.dims), defer,
-                        _p(wslab), int(wgn), ctypes.cast(table, ctypes.c_void_p), len(folds), st)
-                folds = table = None
-                if wgn:  # dW1_{l+1} lands after its dW2 | db2 | db1 (wgrad_next's layout)
-                    job = _lib.SlabJob(wslab.data_ptr(), wgrad_next.data_ptr() + 4 * _Z_W1_OFF,
-                                       HIDDEN * HIDDEN, nz, 0)
-                    # (one partial per walking workgroup — per tile at small batches:
-                    # reduced by this layer's agg-free backward, the next launch,
-                    # whose grid leaves room; else with the chain's final reduce)
-                    if FOLD_SLABS and agg is None:
-                        w1_fold = (job, wslab)
-                    else:
-                        jobs.append(job)
-                        keep.append(wslab)
-                wslab = dz1_next = w1_next = wgrad_next = None
-            else:
-                folds = take_folds(1)
-                _launch("scgib_gin_bwd_stats_bn_fold", {"n": n, "e": gr.edge_capacity(), "d_in": HIDDEN},
-                        _p(dagg_next), _p(gr.rowptr_t),
-                        _p(gr.col_t), ctx.opes[l + 1], _p(z2), _p(stat), n, int(ctx.training),
-                        _p(dy), _p(bn_g[0]), _p(bn_g[1]), _p(coef), _p(bn_ws), _p(cnt),
-                        _p(gr.dims), defer, _byref(folds[0][0] if folds else None), st)
-                folds = dagg_next = None
-            bpend = _lib.BnBwdPending(gpart, bn_g[0].data_ptr(), bn_g[1].data_ptr(),
-                                      int(ctx.training)) if defer else None
-            meta = {"n": n, "e": gr.edge_capacity(), "d_in": d_in, "r": r is not None}
+            fold0 = pre and l == 0
+            self.stats(l, z2, stat, agg is None)
+            bpend = _lib.BnBwdPending(self.gpart, self.bn_g[0].data_ptr(), self.bn_g[1].data_ptr(),
+                                      int(ctx.training)) if self.defer else None
             w1c, w2c = _f32(w1, "w1"), _f32(w2, "w2")
-            b1c = _f32(b1, "b1") if r is None else None
+            lay = (agg, r, z2, stat, w1c, _f32(b1, "b1") if r is None else None, w2c)
             # (frozen-weight kernels: stored r, d_in = 64 or the layer-0 fold)
             wg = need is None or any(need[6 * l: 6 * l + 4]) or r is None or \
-                (d_in != HIDDEN and not (pre and l == 0))
-            meta["wg"] = wg
-            grads[6 * l + 4] = bn_g[0]
-            grads[6 * l + 5] = bn_g[1]
-            if agg is None:
-                # agg-free: dz1 out, dW2 | db2 | db1 here, dW1 from layer l - 1's
-                # statistics launch (always one: l >= 1); a frozen layer (not
-                # wg): the same dz1 chain, no weight products
-                meta["z"] = True
-                nsz = int(_lib.query("scgib_gin_layer_bwd_z_slabs", n))
-                slab = torch.empty(nsz * _Z_SLAB, dtype=torch.float32, device=dev) if wg else None
-                dz1 = torch.empty(n, HIDDEN, dtype=torch.float32, device=dev)
-                f2 = take_folds(1)  # the previous agg-free layer's dW2 | db slab (pend)
-                _launch("scgib_gin_layer_bwd_z", meta, _p(dy), _p(z2), _p(r), _p(stat), _p(coef),
-                        _p(w2c), n, _p(dz1), _p(slab), int(wg), _p(gr.dims), _byref(bpend),
-                        _byref(w1_fold[0] if w1_fold else None), _byref(f2[0][0] if f2 else None),
-                        st)
-                w1_fold = f2 = None
-                wgrad = None
-                if wg:
-                    wgrad = torch.empty(_Z_SLAB + HIDDEN * HIDDEN, dtype=torch.float32,
-                                        device=dev)
-                    pend_jobs.append((_lib.SlabJob(slab.data_ptr(), wgrad.data_ptr(), _Z_SLAB,
-                                                   nsz, 0), slab))
-                    grads[6 * l + 2] = wgrad[:HIDDEN * HIDDEN].view(HIDDEN, HIDDEN)
-                    grads[6 * l + 3] = wgrad[HIDDEN * HIDDEN:HIDDEN * HIDDEN + HIDDEN]
-                    grads[6 * l + 1] = wgrad[HIDDEN * HIDDEN + HIDDEN:_Z_SLAB]
-                    grads[6 * l + 0] = wgrad[_Z_W1_OFF:].view(HIDDEN, HIDDEN)
-                dz1_next, w1_next, wgrad_next = dz1, w1c, wgrad
-                slab = dz1 = wgrad = None
-                yield
-                continue
-            if pre and l == 0:
-                width = int(_lib.query("scgib_gin_layer0_slab_width"))
-                # (dwt_row: one spare row whose d Wt columns another encoder's
-                # reduce fills — the pair's core chain — so this encoder's
-                # final reduce returns the sum of both, _GinEncoderPair)
-                xrow = int(getattr(ctx, "dwt_row", False))
-                slab = torch.empty((nslab + xrow) * width, dtype=torch.float32, device=dev)
-                _launch("scgib_gin_layer0_bwd", meta, _p(dy), _p(z2), _p(r), _p(agg), _p(aggx),
-                        ctx.n_feat, _p(stat), _p(coef), _p(w1c), _p(b1c), _p(w2c), n, _p(slab),
-                        int(wg), _p(gr.dims), _byref(bpend), st)
-                dagg = None
-            else:
-                width = HIDDEN * HIDDEN + HIDDEN * d_in + 2 * HIDDEN
-                slab = torch.empty(int(_lib.query("scgib_gin_slab_floats", n, d_in)),
-                                   dtype=torch.float32, device=dev) if wg else None
-                dagg = torch.empty(n, d_in, dtype=torch.float32, device=dev)
-                _launch("scgib_gin_layer_bwd", meta, _p(dy), _p(z2), _p(r), _p(agg), d_in,
-                        _p(stat), _p(coef), _p(w1c), _p(b1c), _p(w2c), n, _p(dagg), _p(slab),
-                        _NULL, int(wg), _p(gr.dims), _byref(bpend), st)
-            if not wg:  # no weight gradients: only layer 0's dWt (its slab's tail)
-                if pre and l == 0:
-                    o = HIDDEN * HIDDEN + HIDDEN * d_in + 2 * HIDDEN
-                    into = getattr(ctx, "dwt_into", None)
-                    if into is None:
-                        dwt = torch.empty(32 * ctx.n_feat, dtype=torch.float32, device=dev)
-                    jobs.append(_lib.SlabJob(slab.data_ptr() + 4 * o,
-                                             into if into is not None else dwt.data_ptr(),
-                                             32 * ctx.n_feat, nslab + xrow, width))
-                    keep.append(slab)
-                    if xrow:
-                        ctx.dwt_row_ptr = slab.data_ptr() + 4 * (nslab * width + o)
-                        ctx.dwt_row_slab = slab
-                    dwt = dwt.view(32, ctx.n_feat) if into is None else None
-                dagg_next = dagg
-                yield
-                continue
-            wgrad = torch.empty(width, dtype=torch.float32, device=dev)
-            if pre and l == 0:  # dWt occupies 32 * F of its 512 columns
-                o = HIDDEN * HIDDEN + HIDDEN * d_in + 2 * HIDDEN
-                into = getattr(ctx, "dwt_into", None)
-                if into is None and not xrow:
-                    jobs.append(_lib.SlabJob(slab.data_ptr(), wgrad.data_ptr(),
-                                             o + 32 * ctx.n_feat, nslab, width))
-                else:  # dWt as its own job: into another encoder's row / over the spare row
-                    jobs.append(_lib.SlabJob(slab.data_ptr(), wgrad.data_ptr(), o, nslab, width))
-                    jobs.append(_lib.SlabJob(slab.data_ptr() + 4 * o,
-                                             into if into is not None else wgrad.data_ptr() + 4 * o,
-                                             32 * ctx.n_feat, nslab + xrow, width))
-                if xrow:
-                    ctx.dwt_row_ptr = slab.data_ptr() + 4 * (nslab * width + o)
-                    ctx.dwt_row_slab = slab
-                keep.append(slab)
-            else:  # reduced by the next stats launch, or together at the end
-                ns = int(_lib.query("scgib_gin_layer_bwd_slabs", n, d_in))
-                job = _lib.SlabJob(slab.data_ptr(), wgrad.data_ptr(), width, ns, 0)
-                if FOLD_SLABS and l > 0:
-                    pend_jobs.append((job, slab))
-                else:
-                    jobs.append(job)
-                    keep.append(slab)
-            o = HIDDEN * HIDDEN
-            grads[6 * l + 2] = wgrad[:o].view(HIDDEN, HIDDEN)
-            grads[6 * l + 0] = wgrad[o:o + HIDDEN * d_in].view(HIDDEN, d_in)
-            o += HIDDEN * d_in
-            grads[6 * l + 3] = wgrad[o:o + HIDDEN]
-            grads[6 * l + 1] = wgrad[o + HIDDEN:o + 2 * HIDDEN]
-            if pre and l == 0 and getattr(ctx, "dwt_into", None) is None:
-                o += 2 * HIDDEN
-                dwt = wgrad[o:o + 32 * ctx.n_feat].view(32, ctx.n_feat)
-            dagg_next = dagg
-            yield
-        for job, sl in pend_jobs:  # (none past layer 0's statistics launch as a rule)
-            jobs.append(job)
-            keep.append(sl)
-        pend_jobs = None
-        extra = getattr(ctx, "extra_jobs", None)
-        if extra is not None:  # deferred loss-section slabs (SlabScope), same launch
-            ctx.extra_jobs = None
-            jobs.extend(extra[0])
-            keep.extend(extra[1])
-        if jobs and getattr(ctx, "defer_final", False):  # enqueued by the caller (the pair)
-            ctx.final = (jobs, keep)
-        elif jobs:  # every layer's weight-gradient slabs, one fixed-order reduce launch
-            _reduce_jobs(jobs, st)
-            del keep  # slabs stay allocated until the launch is enqueued
+                (d_in != HIDDEN and not fold0)
+            meta = {"n": self.n, "e": gr.edge_capacity(), "d_in": d_in, "r": r is not None,
+                    "wg": wg}
+            grads[6 * l + 4], grads[6 * l + 5] = self.bn_g[0], self.bn_g[1]
+            layer = self.layer_z if agg is None else self.layer0 if fold0 else self.layer_plain
+            views, work = layer(lay, meta, wg, bpend)
+            # reduced by the next statistics launch, or (layer 0, no folding) at the end
+            (self.pend if agg is None or (FOLD_SLABS and l > 0) else self.final).extend(work)
+            if views is not None:
+                grads[6 * l: 6 * l + 4] = views
+            views = work = lay = None
+            _layer_stamp(links.stamp_tag, L - 1 - l)
+        final = self.final + self.pend  # (none pending past layer 0's statistics launch as a rule)
+        if links.first_fold is not None:  # (no statistics launch took it)
+            final.append(links.first_fold)
+        final.extend(links.extra)  # deferred loss-section slabs (SlabScope), same launch
+        self.final = self.pend = links.first_fold = None
+        links.extra = ()
+        if final and links.defer_final:  # enqueued by the caller (the pair)
+            links.final = final
+        else:  # every layer's weight-gradient slabs, one fixed-order reduce launch
+            _reduce_work(final, self.st)
+        final = None  # slabs stay allocated until the launch is enqueued
         if pre:
-            return (None, None, None, None, None, dwt, None, *grads)
+            return (None, None, None, None, None, self.dwt, None, *grads)
         # d h0 = (1+eps_0) d(agg_0) + sum over out-edges (transposed aggregation)
-        dh0 = _aggregate(dagg_next, gr.rowptr_t, gr.col_t, ctx.opes[0], gr.dims)
+        dh0 = _aggregate(self.dagg_next, gr.rowptr_t, gr.col_t, ctx.opes[0], gr.dims)
         return (dh0, None, None, None, None, None, None, *grads)
 
 
@@ -1071,11 +1109,7 @@ def gin_encoder_x(x, graph, gin, transfer, node_map=None):
     graph's rows to rows of ``x`` (ego batches: ego.ndata['_ID'])."""
     if graph.num_nodes() == 0:
         raise _lib.ScgibError("gin_encoder on an empty graph")
-    if transfer.bias is not None or transfer.weight.shape != (32, x.shape[1]) \
-            or x.shape[1] > 16:
-        raise _lib.ScgibError("transfer_d fold needs Linear(F <= 16, 32, bias=False)")
-    if x.requires_grad:
-        raise _lib.ScgibError("transfer_d fold: no gradient w.r.t. the raw features")
+    _check_transfer_fold(x, transfer)
     return _GinEncoder.apply(None, graph, gin, bool(gin.training), x, transfer.weight,
                              node_map, *_gin_layer_params(gin))
 
@@ -1316,16 +1350,14 @@ class _GinEncoderPair(torch.autograd.Function):
             core_tail()
         # Encoder2 + its readout (dgl.sum_nodes per ego-net) on ``side``,
         # Encoder1 on the current stream, one chain after the other
-        ego_steps = _GinEncoder.forward_steps(
-            ctx.sub[0], None, ego, gin_ego, training, x, wt, nmap, *params[:ne],
-            readout=(ego.graph_ptr, ego.batch_size, ego.seg_dims))
         fuse_tail = ctx.lin and FUSE_ENC_TAIL and core.num_nodes() > 0
-        core_steps = _GinEncoder.forward_steps(ctx.sub[1], None, core, gin_core, training, x, wt,
-                                               None, *params[ne:], stop_before_apply=fuse_tail)
         with torch.cuda.stream(side):
-            s, ro = _drain(ego_steps, "fwd.ego")
+            s, ro = _GinEncoder.forward(
+                ctx.sub[0], None, ego, gin_ego, training, x, wt, nmap, *params[:ne],
+                readout=(ego.graph_ptr, ego.batch_size, ego.seg_dims), stamp_tag="fwd.ego")
             stamp("fwd.ego_end[side]")
-        f = _drain(core_steps, "fwd.core")
+        f = _GinEncoder.forward(ctx.sub[1], None, core, gin_core, training, x, wt, None,
+                                *params[ne:], stop_before_apply=fuse_tail, stamp_tag="fwd.core")
         stamp("fwd.core_end[main]")
         outs = (s, ro, f)
         if ctx.lin:  # compressor[0] on the (shorter) core chain, before the join
@@ -1385,69 +1417,55 @@ class _GinEncoderPair(torch.autograd.Function):
         scope = ctx.scope if (ctx.scope is not None and ctx.scope.open) else None
         held = None
         need = ctx.needs_input_grad[12:]  # the two encoders' parameters (frozen ones skip dW)
-        ctx.sub[0].need, ctx.sub[1].need = need[:ctx.ne], need[ctx.ne:]
-        dw0 = db0 = None
+        dw0 = db0 = lin_slab = None  # (lin_slab: compressor[0]'s slab, held until this returns)
         g_f_in = g_f
         # the critical ego chain is captured first: the replayed graph then
-        # puts it on the interaction's queue (round 2: 0.4381 -> 0.4326 ms)
-        ctx.sub[0].stamp_tag = "bwd.ego"
+        # puts it on the interaction's queue (round 2: 0.4381 -> 0.4326 ms).
         # d Wt = d Wt(ego) + d Wt(core) without a separate add after the join:
         # the core chain's reduce writes its d Wt into a spare row of the ego
         # layer-0 slab, and the ego chain's final reduce — enqueued after the
         # join, which costs nothing there (the core chain ends first) — sums
         # it with the ego's rows
-        ctx.sub[0].dwt_row = ctx.sub[0].defer_final = True
+        ego = _ChainLinks(need=need[:ctx.ne], stamp_tag="bwd.ego", spare_dwt_row=True,
+                          defer_final=True)
+        core = _ChainLinks(need=need[ctx.ne:], stamp_tag="bwd.core")
         later = scope.take_later() if scope is not None else []
-        ge = _GinEncoder.backward(ctx.sub[0], g_s, g_ro)
+        ge = _GinBackward(ctx.sub[0], ego, g_s, g_ro).run()
         for launch, _ in later:  # deferred weight-gradient launches, after the ego chain
             launch()
         later = None
         stamp("bwd.ego_end[main]")
-        row = getattr(ctx.sub[0], "dwt_row_ptr", None)
-        if row is not None:
-            ctx.sub[1].dwt_into = row
-            ctx.sub[0].dwt_row_slab.record_stream(side)
+        if ego.dwt_row_ptr is not None:
+            core.dwt_into = ego.dwt_row_ptr
+            ego.dwt_row_slab.record_stream(side)
         with torch.cuda.stream(side):
             if ctx.lin and g_t is not None:
                 f, w0 = ctx.lin_saved
                 g_t = _f32(g_t, "compressor.0 grad")
-                n = f.shape[0]
-                slab = torch.empty(int(_lib.query("scgib_linear_slab_floats", n)),
-                                   dtype=torch.float32, device=f.device)
-                wg = torch.empty(HIDDEN * HIDDEN + HIDDEN, dtype=torch.float32, device=f.device)
-                df_total = torch.empty_like(f)
-                lin_defer = scope is not None and scope.usable(ctx.lin_leaves)
-                _lib.call("scgib_linear_bwd", _p(g_t), _p(f), _p(w0), n,
-                          _p(_f32(g_f, "g_f")) if g_f is not None else None, _p(df_total),
-                          _p(slab), None if lin_defer else _p(wg), _p(ctx.core_dims), _stream())
-                if lin_defer:
-                    scope.add(slab, wg, wg.numel(), slab.numel() // wg.numel())
-                dw0, db0 = wg[: HIDDEN * HIDDEN].view(HIDDEN, HIDDEN), wg[HIDDEN * HIDDEN:]
-                g_f = df_total
+                g_f, dw0, db0, lin_slab = _linear_bwd(g_t, f, w0, g_f, ctx.core_dims, scope,
+                                                      ctx.lin_leaves)
             if scope is not None:
-                jobs, keep = scope.take()
-                for tsr in keep:  # made on the main stream, reduced / written on side
-                    tsr.record_stream(side)
+                work = scope.take()
+                for w in work:  # made on the main stream, reduced / written on side
+                    for tsr in w.owns:
+                        tsr.record_stream(side)
                 # ... and referenced until after the join below: a block made on
                 # main and read on side is not returned to the allocator while
                 # later main-stream work could be handed it unordered (in a
                 # captured step `record_stream` alone does not order the reuse)
-                held = list(keep)
-                if jobs and FOLD_SLABS:  # the largest (the head MLP's) into Encoder1's first launch
-                    big = max(range(len(jobs)), key=lambda i: jobs[i].width * jobs[i].n_slabs)
-                    ctx.sub[1].first_fold = (jobs[big], keep[2 * big: 2 * big + 2])
-                    jobs = jobs[:big] + jobs[big + 1:]
-                    keep = keep[:2 * big] + keep[2 * big + 2:]
-                ctx.sub[1].extra_jobs = (jobs, keep)
-            gc = _drain(_GinEncoder.backward_steps(ctx.sub[1], g_f), "bwd.core")
+                held = list(work)
+                if work and FOLD_SLABS:  # the largest (the head MLP's) into Encoder1's first launch
+                    core.first_fold = work.pop(max(
+                        range(len(work)), key=lambda i: work[i].job.width * work[i].job.n_slabs))
+                core.extra = work
+            gc = _GinBackward(ctx.sub[1], core, g_f).run()
             if ctx.bwd_tail is not None:  # e.g. NoisePrefetch.draw: the next step's noise
                 ctx.bwd_tail()
             stamp("bwd.core_end[side]")
         main.wait_stream(side)
         stamp("bwd.joined[main]")
-        final = getattr(ctx.sub[0], "final", None)
+        final, ego.final = ego.final, None
         if final is not None:  # the ego chain's weight-gradient reduce, d Wt(core) included
-            ctx.sub[0].final = None
             # left to the optimizer step that follows (fuse_final_into_step) — only
             # when autograd will take the views of the buffers this reduce writes
             # over as .grad (no kernel): with a .grad already there (gradient
@@ -1459,13 +1477,12 @@ class _GinEncoderPair(torch.autograd.Function):
             else:
                 # (an earlier backward's reduce still pending — accumulation
                 # that began from .grad None: autograd is about to read its output)
-                for jobs, _keep in _FINAL_PENDING.pop(main.device_index or 0, []):
-                    _reduce_jobs(jobs, _stream())
-                _reduce_jobs(final[0], _stream())
+                reduce_pending(_FINAL_PENDING.pop(main.device_index or 0, []) + [final])
             final = None
-        ctx.sub[0].dwt_row_slab = None
-        if ctx.side_tail is not None and hasattr(ctx.side_tail, "joined"):
-            ctx.side_tail.joined()  # ordered before main's later work by the join above
+        ego.dwt_row_slab = None
+        side_tail = ctx.side_tail
+        if side_tail is not None and hasattr(side_tail, "joined"):
+            side_tail.joined()  # ordered before main's later work by the join above
         held = None  # after the join: main-stream reuse is ordered after side's reads
         for g in (*gc, dw0, db0):
             if isinstance(g, torch.Tensor):
@@ -1477,6 +1494,24 @@ class _GinEncoderPair(torch.autograd.Function):
         dwt = ge[5] if gc[5] is None else ge[5] + gc[5]  # (gc[5] None: summed by the reduce)
         return (None, dwt, dw0, db0, None, None, None, None, None, None, None, None, *ge[7:],
                 *gc[7:])
+
+
+def _linear_bwd(g_t, f, w0, g_f, dims, scope=None, leaves=()):
+    """(d f, dW0, db0, the slab) of compressor[0]'s backward launch: d f = g_f +
+    g_t W0 (g_f None: zero); dW0 | db0 reduced by the launch itself or, where
+    ``scope`` can take them for ``leaves``, by the encoder pair's deferred reduce."""
+    n = f.shape[0]
+    slab = torch.empty(int(_lib.query("scgib_linear_slab_floats", n)), dtype=torch.float32,
+                       device=f.device)
+    wg = torch.empty(HIDDEN * HIDDEN + HIDDEN, dtype=torch.float32, device=f.device)
+    df_total = torch.empty_like(f)
+    defer = scope is not None and scope.usable(leaves)
+    _lib.call("scgib_linear_bwd", _p(g_t), _p(f), _p(w0), n,
+              _p(_f32(g_f, "g_f")) if g_f is not None else None, _p(df_total), _p(slab),
+              None if defer else _p(wg), _p(dims), _stream())
+    if defer:
+        scope.add(slab, wg, wg.numel(), slab.numel() // wg.numel())
+    return df_total, wg[: HIDDEN * HIDDEN].view(HIDDEN, HIDDEN), wg[HIDDEN * HIDDEN:], slab
 
 
 def _torch_stream():
@@ -1500,11 +1535,7 @@ def gin_encoder_pair_x(x, ego, gin_ego, core, gin_core, transfer, node_map, side
     chain, before that join."""
     if ego.num_nodes() == 0 or core.num_nodes() == 0:
         raise _lib.ScgibError("gin_encoder on an empty graph")
-    if transfer.bias is not None or transfer.weight.shape != (32, x.shape[1]) \
-            or x.shape[1] > 16:
-        raise _lib.ScgibError("transfer_d fold needs Linear(F <= 16, 32, bias=False)")
-    if x.requires_grad:
-        raise _lib.ScgibError("transfer_d fold: no gradient w.r.t. the raw features")
+    _check_transfer_fold(x, transfer)
     if bool(gin_ego.training) != bool(gin_core.training):
         raise _lib.ScgibError("gin_encoder_pair_x: encoders in different train/eval modes")
     w0, b0 = (lin0.weight, lin0.bias) if lin0 is not None else (None, None)
@@ -1547,6 +1578,21 @@ def sum_nodes_graph(graph, x):
     return segment_sum(x, graph.graph_ptr, graph.batch_size)
 
 
+def _lstm_wgrads(ctx, d, device):
+    """(buffer, views, their pointer arguments, deferred?): the Set2Set LSTM's
+    dW_ih, dW_hh, db_ih, db_hh as views of one buffer — autograd takes the views
+    themselves as .grad (a gradient tensor referenced elsewhere is copied at
+    accumulation) while a deferred launch keeps the buffer — and whether they are
+    written past the encoders' backward (SlabScope.defer: the encoder pair's
+    scope can take them, nothing reads them before the optimizer)."""
+    n_ih, n_hh = 4 * d * 2 * d, 4 * d * d
+    wbuf = torch.empty(n_ih + n_hh + 8 * d, dtype=torch.float32, device=device)
+    views = (wbuf[:n_ih].view(4 * d, 2 * d), wbuf[n_ih:n_ih + n_hh].view(4 * d, d),
+             wbuf[n_ih + n_hh:n_ih + n_hh + 4 * d], wbuf[n_ih + n_hh + 4 * d:])
+    ptrs = tuple(ctypes.c_void_p(v.data_ptr()) for v in views)
+    return wbuf, views, ptrs, ctx.scope is not None and ctx.scope.usable(ctx.leaves)
+
+
 class _Set2Set(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_ih, b_ih, w_hh, b_hh, ptr, nseg, n_iters):
@@ -1577,29 +1623,14 @@ class _Set2Set(torch.autograd.Function):
         dx = torch.empty_like(x)
         dgates = torch.empty(max(ctx.nseg * ctx.n_iters * 4 * d, 1), dtype=torch.float32,
                              device=x.device)
-        # the four weight gradients as views of one buffer: autograd then takes
-        # the views themselves as .grad (a gradient tensor referenced elsewhere
-        # is copied at accumulation), while the deferred launch keeps the buffer
-        n_ih, n_hh = 4 * d * 2 * d, 4 * d * d
-        wbuf = torch.empty(n_ih + n_hh + 8 * d, dtype=torch.float32, device=x.device)
-        dw_ih = wbuf[:n_ih].view(4 * d, 2 * d)
-        dw_hh = wbuf[n_ih:n_ih + n_hh].view(4 * d, d)
-        db_ih = wbuf[n_ih + n_hh:n_ih + n_hh + 4 * d]
-        db_hh = wbuf[n_ih + n_hh + 4 * d:]
-        ptrs = (dw_ih.data_ptr(), dw_hh.data_ptr(), db_ih.data_ptr(), db_hh.data_ptr())
-        # the LSTM weight gradients: deferred past the encoders' backward when
-        # the encoder pair's scope can take them (nothing reads them before the
-        # optimizer), else in the same call
-        scope = getattr(ctx, "scope", None)
-        defer = scope is not None and scope.usable(ctx.leaves)
-        wg = (None,) * 4 if defer else tuple(ctypes.c_void_p(v) for v in ptrs)
+        wbuf, (dw_ih, dw_hh, db_ih, db_hh), ptrs, defer = _lstm_wgrads(ctx, d, x.device)
         _lib.call("scgib_set2set_bwd", _p(x), _p(ctx.ptr), ctx.nseg, d, ctx.n_iters, _p(w_ih),
-                  _p(w_hh), _p(save), _p(g), _p(dx), x.shape[0], _p(dgates), *wg, _stream())
+                  _p(w_hh), _p(save), _p(g), _p(dx), x.shape[0], _p(dgates),
+                  *((None,) * 4 if defer else ptrs), _stream())
         if defer:
-            args = (_p(save), _p(dgates), ctx.nseg, d, ctx.n_iters,
-                    *(ctypes.c_void_p(v) for v in ptrs))
-            scope.defer(lambda: _lib.call("scgib_set2set_wgrad", *args, _stream()),
-                        save, dgates, wbuf)
+            args = (_p(save), _p(dgates), ctx.nseg, d, ctx.n_iters, *ptrs)
+            ctx.scope.defer(lambda: _lib.call("scgib_set2set_wgrad", *args, _stream()),
+                            save, dgates, wbuf)
         return dx, dw_ih, db_ih, dw_hh, db_hh, None, None, None
 
 
@@ -1652,26 +1683,15 @@ class _Set2SetPair(torch.autograd.Function):
         dxa, dxb = torch.empty_like(xa), torch.empty_like(xb)
         dgates = torch.empty(max(2 * ctx.nseg * ctx.n_iters * 4 * d, 1), dtype=torch.float32,
                              device=xa.device)
-        n_ih, n_hh = 4 * d * 2 * d, 4 * d * d
-        wbuf = torch.empty(n_ih + n_hh + 8 * d, dtype=torch.float32, device=xa.device)
-        dw_ih = wbuf[:n_ih].view(4 * d, 2 * d)
-        dw_hh = wbuf[n_ih:n_ih + n_hh].view(4 * d, d)
-        db_ih = wbuf[n_ih + n_hh:n_ih + n_hh + 4 * d]
-        db_hh = wbuf[n_ih + n_hh + 4 * d:]
-        ptrs = (dw_ih.data_ptr(), dw_hh.data_ptr(), db_ih.data_ptr(), db_hh.data_ptr())
-        # the LSTM weight gradients (both inputs' rounds, one pass): deferred
-        # past the encoders' backward as _Set2Set's are (SlabScope)
-        scope = getattr(ctx, "scope", None)
-        defer = scope is not None and scope.usable(ctx.leaves)
-        wg = (None,) * 4 if defer else tuple(ctypes.c_void_p(v) for v in ptrs)
+        # (the LSTM weight gradients of both inputs' rounds, one pass)
+        wbuf, (dw_ih, dw_hh, db_ih, db_hh), ptrs, defer = _lstm_wgrads(ctx, d, xa.device)
         _lib.call("scgib_set2set_bwd2", _p(xa), _p(xb), _p(ctx.ptr), ctx.nseg, d, ctx.n_iters,
                   _p(w_ih), _p(w_hh), _p(save), _p(ga), _p(gb), _p(dxa), _p(dxb), xa.shape[0],
-                  _p(dgates), *wg, _stream())
+                  _p(dgates), *((None,) * 4 if defer else ptrs), _stream())
         if defer:
-            args = (_p(save), _p(dgates), 2 * ctx.nseg, d, ctx.n_iters,
-                    *(ctypes.c_void_p(v) for v in ptrs))
-            scope.defer(lambda: _lib.call("scgib_set2set_wgrad", *args, _stream()),
-                        save, dgates, wbuf)
+            args = (_p(save), _p(dgates), 2 * ctx.nseg, d, ctx.n_iters, *ptrs)
+            ctx.scope.defer(lambda: _lib.call("scgib_set2set_wgrad", *args, _stream()),
+                            save, dgates, wbuf)
         return dxa, dxb, dw_ih, db_ih, dw_hh, db_hh, None, None, None
 
 
@@ -2045,14 +2065,14 @@ def _interaction_backward(ctx, saved, g_im, g_z1, g_z2, g_kl, g_klmean):
     ds = torch.empty_like(s)
     pgrad = torch.empty(max(B, 1), PGRAD_STRIDE, dtype=torch.float32, device=dev)
     pg = torch.empty(PGRAD_STRIDE, dtype=torch.float32, device=dev)
-    scope = getattr(ctx, "scope", None)
+    scope = ctx.scope  # (None: _InteractionLin, or no encoder pair to defer into)
     defer = B > 0 and scope is not None and scope.usable(ctx.leaves)
     bwd_args = (_p(g_im), _p(g_z1), _p(g_z2), _p(g_kl), _p(f), _p(t),
                 _p(s), _p(u_feat), _p(ctx.graph.graph_ptr), B, n, _p(gamma), _p(beta),
                 _p(ctx.rm), _p(ctx.rv), ctx.bn_eps, int(ctx.training), _p(w2), _p(w_att),
                 _p(z1), _p(lam), _p(logit), _p(stats), _p(df), _p(dt), _p(ds), _p(pgrad),
                 _p(g_klmean), int(ctx.pad), None if defer else _p(pg))
-    use_att = getattr(ctx, "use_att", True)
+    use_att = ctx.use_att  # (set by _interaction_forward)
     if use_att:
         _launch("scgib_interaction_bwd", {"n": n, "B": B}, *bwd_args, _stream())
     else:
@@ -2096,6 +2116,7 @@ class _InteractionLin(torch.autograd.Function):
     def forward(ctx, f, w0, b0, s, u_gate, u_feat, gamma, beta, w2, b2, w_att, b_att, graph, bn,
                 training, use_att=True):
         ctx.set_materialize_grads(False)  # outputs no loss reads (fine-tune: z1, z2, KL): no fills
+        ctx.leaves, ctx.scope = (), None  # (this op's reduces are never deferred)
         f = _f32(f, "interaction")
         s = _f32(s, "interaction")
         w0, b0 = _f32(w0, "compressor.0.weight"), _f32(b0, "compressor.0.bias")
@@ -2115,15 +2136,7 @@ class _InteractionLin(torch.autograd.Function):
         w0 = saved[-1]
         df, dt, ds, grads = _interaction_backward(ctx, saved[:-1], g_im, g_z1, g_z2, g_kl,
                                                   g_klmean)
-        f = saved[0]
-        n = f.shape[0]
-        slab = torch.empty(int(_lib.query("scgib_linear_slab_floats", n)), dtype=torch.float32,
-                           device=f.device)
-        wg = torch.empty(HIDDEN * HIDDEN + HIDDEN, dtype=torch.float32, device=f.device)
-        df_total = torch.empty_like(f)
-        _lib.call("scgib_linear_bwd", _p(dt), _p(f), _p(w0), n, _p(df), _p(df_total), _p(slab),
-                  _p(wg), _p(ctx.graph.dims), _stream())
-        dw0, db0 = wg[: HIDDEN * HIDDEN].view(HIDDEN, HIDDEN), wg[HIDDEN * HIDDEN:]
+        df_total, dw0, db0, _slab = _linear_bwd(dt, saved[0], w0, df, ctx.graph.dims)
         return (df_total, dw0, db0, ds, None, None) + grads + (None, None, None, None)
 
 
@@ -2453,12 +2466,7 @@ class _Mlp2(torch.autograd.Function):
                   _p(slab), None if defer else _p(wg), _p(ctx.dims), _stream())
         if defer:  # reduced by the encoder pair's backward (SlabScope)
             ctx.scope.add(slab, wg, wg.numel(), slab.numel() // wg.numel())
-        o = HIDDEN * HIDDEN
-        dw2 = wg[:o].view(HIDDEN, HIDDEN)
-        dw1 = wg[o: o + HIDDEN * d_in].view(HIDDEN, d_in)
-        db2 = wg[o + HIDDEN * d_in: o + HIDDEN * d_in + HIDDEN]
-        db1 = wg[o + HIDDEN * d_in + HIDDEN:]
-        return dx, dw1, db1, dw2, db2, None
+        return (dx, *_mlp2_grad_views(wg, d_in), None)
 
 
 def mlp2(x, mlp, dims=None):
@@ -2510,12 +2518,7 @@ class _Mlp2Recon(torch.autograd.Function):
                   _p(gr.rowptr), _p(gr.col), None if sym else _p(gr.rowptr_t),
                   None if sym else _p(gr.col_t), _p(g_loss), _p(dx), _p(slab), _p(wg),
                   _p(gr.dims), _stream())
-        o = HIDDEN * HIDDEN
-        dw2 = wg[:o].view(HIDDEN, HIDDEN)
-        dw1 = wg[o: o + HIDDEN * d_in].view(HIDDEN, d_in)
-        db2 = wg[o + HIDDEN * d_in: o + HIDDEN * d_in + HIDDEN]
-        db1 = wg[o + HIDDEN * d_in + HIDDEN:]
-        return dx, dw1, db1, dw2, db2, None
+        return (dx, *_mlp2_grad_views(wg, d_in), None)
 
 
 class _Mlp2ReconContrastive(torch.autograd.Function):
@@ -2588,12 +2591,7 @@ class _Mlp2ReconContrastive(torch.autograd.Function):
                   _p(cws), _p(g_con), _p(dz1), _p(dz2), _p(ccnt), _stream())
         if defer:  # reduced by the encoder pair's backward (SlabScope)
             ctx.scope.add(slab, wg, wg.numel(), slab.numel() // wg.numel())
-        o = HIDDEN * HIDDEN
-        dw2 = wg[:o].view(HIDDEN, HIDDEN)
-        dw1 = wg[o: o + HIDDEN * d_in].view(HIDDEN, d_in)
-        db2 = wg[o + HIDDEN * d_in: o + HIDDEN * d_in + HIDDEN]
-        db1 = wg[o + HIDDEN * d_in + HIDDEN:]
-        return dx, dw1, db1, dw2, db2, None, dz1, dz2
+        return (dx, *_mlp2_grad_views(wg, d_in), None, dz1, dz2)
 
 
 def mlp2_recon_contrastive(x, mlp, graph, z1, z2):
@@ -3005,6 +3003,13 @@ def _gt_layer_bwd(g, saved, gr, heads, training, slabs, dh, st):
               _p(dp1), n, _p(dh), _p(slabs[3]), _p(gr.dims), st)
 
 
+def _gt_layer_work(slab, n_slabs, out):
+    """The four reduces of one layer's weight-gradient slab into its row ``out``."""
+    widths, woff = _gt_slab_layout()
+    return [SlabWork(_lib.SlabJob(slab[n_slabs * woff[i]:].data_ptr(), out[woff[i]:].data_ptr(),
+                                  widths[i], n_slabs, 0), (slab,)) for i in range(_GT_SLABS)]
+
+
 def _gt_grad_views(wg, woff):
     """The 16 parameter gradients of a layer (``_GtLayer``'s order) as views of
     its reduced weight-gradient row ``wg``."""
@@ -3048,8 +3053,7 @@ class _GtLayer(torch.autograd.Function):
             slabs = [slab[n_slabs * woff[i]: n_slabs * woff[i + 1]] for i in range(_GT_SLABS)]
             st = _stream()
             _gt_layer_bwd(g, saved, ctx.graph, ctx.heads, ctx.training, slabs, dh, st)
-            _reduce_jobs([_lib.SlabJob(slabs[i].data_ptr(), wg[woff[i]:].data_ptr(), widths[i],
-                                       n_slabs, 0) for i in range(_GT_SLABS)], st)
+            _reduce_work(_gt_layer_work(slab, n_slabs, wg), st)
         return (dh, None, None, None, None, None, *_gt_grad_views(wg, woff))
 
 
@@ -3137,17 +3141,19 @@ def _gt_embed_fwd(x, wt, we, nmap, n, dims, st):
 
 def _gt_embed_bwd(g, x, wt, we, nmap, dims, out, st):
     """The embed's backward launch and its two reduce jobs: dWe | dWt land in
-    ``out`` (scgib_gt_embed_slab_width floats).  Returns (jobs, slab, dWe, dWt)."""
+    ``out`` (scgib_gt_embed_slab_width floats).  Returns (work, dWe, dWt)."""
     n, f = g.shape[0], x.shape[1]
     width = int(_lib.query("scgib_gt_embed_slab_width", f))
     ns = int(_lib.query("scgib_gt_embed_slabs", n))
     slab = torch.empty(ns * width, dtype=torch.float32, device=g.device)
     _lib.call("scgib_gt_embed_bwd", _p(g), _p(x), f, x.shape[0], _p(nmap), _p(wt), _p(we), n,
               _p(slab), _p(dims), st)
-    jobs = [_lib.SlabJob(slab.data_ptr(), out.data_ptr(), _GT_EMBED_WE, ns, width),
-            _lib.SlabJob(slab.data_ptr() + 4 * _GT_EMBED_WE, out[_GT_EMBED_WE:].data_ptr(),
-                         GT_TRANSFER * f, ns, width)]
-    return jobs, slab, out[:_GT_EMBED_WE].view(HIDDEN, GT_TRANSFER), \
+    work = [SlabWork(_lib.SlabJob(slab.data_ptr(), out.data_ptr(), _GT_EMBED_WE, ns, width),
+                     (slab,)),
+            SlabWork(_lib.SlabJob(slab.data_ptr() + 4 * _GT_EMBED_WE,
+                                  out[_GT_EMBED_WE:].data_ptr(), GT_TRANSFER * f, ns, width),
+                     (slab,))]
+    return work, out[:_GT_EMBED_WE].view(HIDDEN, GT_TRANSFER), \
         out[_GT_EMBED_WE:].view(GT_TRANSFER, f)
 
 
@@ -3171,9 +3177,9 @@ class _GtEmbed(torch.autograd.Function):
             return None, torch.zeros_like(wt), torch.zeros_like(we), None, None, None
         out = torch.empty(width, dtype=torch.float32, device=g.device)
         st = _stream()
-        jobs, slab, dwe, dwt = _gt_embed_bwd(g, x, wt, we, ctx.nmap, ctx.dims, out, st)
-        _reduce_jobs(jobs, st)
-        del slab  # (allocated until the reduce is enqueued)
+        work, dwe, dwt = _gt_embed_bwd(g, x, wt, we, ctx.nmap, ctx.dims, out, st)
+        _reduce_work(work, st)
+        del work  # (the slab stays allocated until the reduce is enqueued)
         return None, dwt, dwe, None, None, None
 
 
@@ -3254,7 +3260,7 @@ class _GtEncoderX(torch.autograd.Function):
         n_live = sum(layer_need[lowest:])
         wg = torch.empty(n_live * lw + ew, dtype=torch.float32, device=dev)
         n_slabs = int(_lib.query("scgib_gt_slabs", n))
-        jobs, keep, row = [], [], 0
+        work, row = [], 0
         grads = [None] * (16 * L)
         for l in reversed(range(lowest, L)):
             slab = torch.empty(n_slabs * lw, dtype=torch.float32, device=dev)
@@ -3265,20 +3271,16 @@ class _GtEncoderX(torch.autograd.Function):
             if layer_need[l]:  # (a frozen layer's slabs are written and never reduced)
                 out = wg[row * lw: (row + 1) * lw]
                 row += 1
-                jobs += [_lib.SlabJob(slabs[i].data_ptr(), out[woff[i]:].data_ptr(), widths[i],
-                                      n_slabs, 0) for i in range(_GT_SLABS)]
-                keep.append(slab)
+                work += _gt_layer_work(slab, n_slabs, out)
                 grads[16 * l: 16 * l + 16] = _gt_grad_views(out, woff)
             g = dh
             slab = slabs = dh = None
         dwt = dwe = None
         if embed_need:
-            ejobs, eslab, dwe, dwt = _gt_embed_bwd(g, x, wt, we, ctx.nmap, gr.dims,
-                                                   wg[n_live * lw:], st)
-            jobs += ejobs
-            keep.append(eslab)
-        _reduce_jobs(jobs, st)
-        del keep  # slabs stay allocated until the launches are enqueued
+            ework, dwe, dwt = _gt_embed_bwd(g, x, wt, we, ctx.nmap, gr.dims, wg[n_live * lw:], st)
+            work += ework
+        _reduce_work(work, st)
+        del work  # slabs stay allocated until the launches are enqueued
         return (*none[:_GtEncoderX.N_ARGS], dwt, dwe, *grads)
 
 

@@ -299,15 +299,16 @@ class Adam(torch.optim.Optimizer):
                         "sync_hyper(); a captured step reads them from the device and would "
                         "not see the change: call sync_hyper() before the capture")
                 self.sync_hyper()
-        pending = []  # the final weight-gradient reduces left to this step (ops.fuse_final_into_step)
+        # the final weight-gradient reduces left to this step (ops.fuse_final_into_step):
+        # one list of ops.SlabWork per backward; they keep the slabs referenced
+        pending = []
         for group in self.param_groups:
             pending += ops.take_final(group["params"][0].device) if group["params"] else []
-        jobs = [j for jl, _ in pending for j in jl]
+        jobs = [w.job for work in pending for w in work]
         if jobs:
             stale = self._unaliased(jobs, ents)
             if stale:  # the reduces all the same (nothing is lost), no update
-                for jl, _ in pending:
-                    ops._reduce_jobs(jl, ops._stream())
+                ops.reduce_pending(pending)
                 raise _lib.ScgibError(
                     "scgib Adam: a final weight-gradient reduce left to this step "
                     "(ops.fuse_final_into_step) does not write the gradients it steps on: " + stale +
@@ -315,8 +316,7 @@ class Adam(torch.optim.Optimizer):
                     "reduces were launched, the parameters are unchanged")
         fused = False
         if normed:  # the norm needs every reduced gradient: the reduces first, then the norm
-            for jl, _ in pending:
-                ops._reduce_jobs(jl, ops._stream())
+            ops.reduce_pending(pending)
             fused = True
             self._norm(ents, self._device(), ops._stream())
         flags = (_lib.OPTIM_NORM if normed else 0) | (_lib.OPTIM_SKIP if normed and
@@ -356,8 +356,7 @@ class Adam(torch.optim.Optimizer):
                 fused = True
                 continue
             if pending and not fused:  # not fusable here: the reduces first, as unfused
-                for jl, _ in pending:
-                    ops._reduce_jobs(jl, st)
+                ops.reduce_pending(pending)
                 fused = True
             starts = range(0, len(ent), self._max)
             for i0 in starts:
@@ -374,8 +373,7 @@ class Adam(torch.optim.Optimizer):
                     _lib.call("scgib_adamw_step" if dec else "scgib_adam_step", *head, *byval,
                               ops._p(cnt), st)
         if pending and not fused:  # (no gradients here at all)
-            for jl, _ in pending:
-                ops._reduce_jobs(jl, ops._stream())
+            ops.reduce_pending(pending)
         if dyn and last is None:  # nothing to step: the call still counts
             _lib.call("scgib_adam_step_dyn", None, 0, *hyper_args(0, True),
                       ops._p(ops.counters(self._device(), "adam", 1)), ops._stream())

@@ -376,9 +376,9 @@ def test_slab_scope_rules(pkg, monkeypatch):
     w.grad = None
     b = ops.SlabScope()  # a second forward before a's backward: neither defers
     assert not a.usable((w,)) and not b.usable((w,))
-    jobs, keep = a.take()
-    assert len(jobs) == 1 and jobs[0].n_slabs == 2 and jobs[0].width == 4
-    assert keep[0] is slab and keep[1] is out
+    (work,) = a.take()  # one entry: the job and the buffers it owns
+    assert work.job.n_slabs == 2 and work.job.width == 4
+    assert len(work.owns) == 2 and work.owns[0] is slab and work.owns[1] is out
     assert not a.usable((w,))
     del b
     c = ops.SlabScope()  # a closed scope does not poison a new one
