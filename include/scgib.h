@@ -1507,6 +1507,68 @@ int scgib_ingest_csr(const void *src, const void *dst, int32_t idx_bytes, int64_
                      int64_t ws_rows, int32_t *rowptr, int32_t *col, int64_t col_cap,
                      int32_t *status, scgib_stream_t stream);
 int scgib_ingest_blob(const scgib_ingest_desc *d, scgib_stream_t stream);
+
+/* Graph cores and significant subgraphs (explain.hip; ops.explain_rank /
+ * ops.core_subgraph / explain.explain_dataset).  Entry points
+ * only: the ABI version does not change.
+ *
+ * lam / logit [n_rows]: what scgib_interaction_fwd writes.  pad != 0 (capacity
+ * mode: n_rows is the row capacity, graph_ptr[n_graphs] the actual count):
+ * rows past the actual count get alpha 0, ranks -1 and mask 0.  Nothing is
+ * read back and no entry uses an atomic: every launch captures and every
+ * result is bitwise reproducible.
+ *
+ * scgib_explain_rank: one wavefront per molecule.  alpha = softmax of logit
+ *   over the molecule (max, sum, normalise in fp32, fixed order); lam_rank /
+ *   alpha_rank [n_rows] int32 = position of the row in its molecule by
+ *   descending key, ties by ascending id, keys compared as floats, NaN after
+ *   every number; centres / weights [n_graphs][top_m]: global row ids and
+ *   alpha of the rows with alpha_rank < top_m in rank order, -1 / 0 past the
+ *   molecule's size.  logit NULL (no attention): only lam_rank is written and
+ *   top_m must be 0.  Keys of the first scgib_explain_stage_rows() rows of a
+ *   molecule are staged in LDS, later rows are read from memory; the ranking
+ *   counts predecessors, n_i^2 / 64 comparisons per lane and key.
+ * scgib_explain_core_mask: mask [n_rows] (bytes, 0 / 1).  rule 0: lam_rank <
+ *   max(1, ceil(n_i * ratio)), evaluated in IEEE double, ratio in (0, 1];
+ *   rule 1: lam >= threshold (NaN never kept).
+ * scgib_explain_core_count / _fill: the subgraph induced on the kept rows
+ *   (dgl.node_subgraph): rows in ascending id, each row's columns in CSR order,
+ *   filtered and relabelled by the batch-wide exclusive prefix of the mask;
+ *   graph_ptr_out[g] = that prefix at graph_ptr[g]; out_id = the kept rows' ids.
+ *   ws: scgib_explain_core_ws_words(n_rows) int32.  count leaves the core's
+ *   (rows, edges) in core_dims (summed in 64 bits; a total above int32 sets
+ *   bit 1 of *err and core_dims to 0).  fill writes at most n_out_cap rows and
+ *   e_out_cap columns; rows past the core's get empty CSR rows and id 0.
+ *   out_id / graph_ptr_out may be NULL (a second CSR of the same rows).
+ *   dims (capacity mode, or NULL): dims[0] = the actual row count.
+ * scgib_explain_store: one wavefront per molecule g of the batch; its rows of
+ *   lam / alpha / lam_rank / alpha_rank go to node_off[ids[g]] of the ds_
+ *   arrays.  ids outside [0, n_molecules) (the eval loader's fill, -1) write
+ *   nothing, and no row at or past total_nodes (the ds_ arrays' length) is
+ *   written.  alpha NULL: only lam and lam_rank. */
+int64_t scgib_explain_stage_rows(void);
+int scgib_explain_rank(const float *lam, const float *logit, const int32_t *graph_ptr,
+                       int64_t n_graphs, int64_t n_rows, int32_t top_m, float *alpha,
+                       int32_t *lam_rank, int32_t *alpha_rank, int32_t *centres, float *weights,
+                       int32_t pad, scgib_stream_t stream);
+int scgib_explain_core_mask(const float *lam, const int32_t *lam_rank, const int32_t *graph_ptr,
+                            int64_t n_graphs, int64_t n_rows, int32_t rule, double ratio,
+                            float threshold, uint8_t *mask, int32_t pad, scgib_stream_t stream);
+int64_t scgib_explain_core_ws_words(int64_t n_rows);
+int scgib_explain_core_count(const uint8_t *mask, const int32_t *rowptr, const int32_t *col,
+                             int64_t n_rows, int32_t *ws, int32_t *core_dims, int32_t *err,
+                             const int32_t *dims, scgib_stream_t stream);
+int scgib_explain_core_fill(const uint8_t *mask, const int32_t *rowptr, const int32_t *col,
+                            const int32_t *graph_ptr, int64_t n_graphs, int64_t n_rows,
+                            const int32_t *ws, const int32_t *core_dims, int32_t *out_rowptr,
+                            int32_t *out_col, int32_t *out_id, int32_t *graph_ptr_out,
+                            int64_t n_out_cap, int64_t e_out_cap, const int32_t *dims,
+                            scgib_stream_t stream);
+int scgib_explain_store(const float *lam, const float *alpha, const int32_t *lam_rank,
+                        const int32_t *alpha_rank, const int32_t *graph_ptr, int64_t n_graphs,
+                        const int32_t *ids, const int64_t *node_off, int64_t n_molecules,
+                        int64_t total_nodes, float *ds_lam, float *ds_alpha, int32_t *ds_lam_rank,
+                        int32_t *ds_alpha_rank, scgib_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

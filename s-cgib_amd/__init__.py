@@ -16,6 +16,8 @@ Layout:
   metric_wrapper.py  MetricWrapper.py-compatible MetricWrapper (NaN-masked losses on the device)
   metrics.py   ROC-AUC (OGB semantics) and TU accuracy of the fine-tune configs; EvalBuffer,
                the device-side score buffer and metrics of an epoch (also a package attribute)
+  explain.py   graph cores and significant subgraphs over a whole dataset (explain_dataset);
+               per batch: ``model.explain(...)`` on the four model classes
   optim.py     one-launch device Adam (drop-in for torch.optim.Adam as the scripts use it)
   cache.py     on-disk CSR cache of a molecule dataset (replaces the pts/ pickles)
   refckpt.py   the reference's whole-module checkpoints, read weights-only
@@ -26,7 +28,7 @@ Layout:
 import importlib
 
 __all__ = ["graph", "ops", "models", "dgl", "dist", "synth", "metrics", "optim", "cache", "refckpt",
-           "metric_wrapper", "_lib"]
+           "metric_wrapper", "explain", "_lib"]
 
 
 _MODEL_NAMES = ("Transformer", "GraphTransformerLayer", "MultiHeadAttentionLayer")

@@ -234,6 +234,17 @@ SIGNATURES = {
     "scgib_ingest_csr": (ctypes.c_int, [_P, _P, _I32, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P,
                                         _I64, _P, _P, _I64, _P, _P]),
     "scgib_ingest_blob": (ctypes.c_int, [_P, _P]),
+    "scgib_explain_stage_rows": (_I64, []),
+    "scgib_explain_rank": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I32, _P, _P, _P, _P, _P, _I32,
+                                          _P]),
+    "scgib_explain_core_mask": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I32, _D, _F, _P, _I32,
+                                               _P]),
+    "scgib_explain_core_ws_words": (_I64, [_I64]),
+    "scgib_explain_core_count": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "scgib_explain_core_fill": (ctypes.c_int, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P,
+                                               _I64, _I64, _P, _P]),
+    "scgib_explain_store": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _P, _P, _P,
+                                           _P, _P]),
 }
 
 

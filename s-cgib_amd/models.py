@@ -489,7 +489,114 @@ def semi_loss(z1, z2, chunk):
     return ops.contrastive(z1, z2)
 
 
-class _SCGIBCore(nn.Module):
+class Explanation:
+    """What ``explain`` reads off a batch.  Per atom, [N]:
+    ``lam`` (the preservation gate), ``alpha`` (the attention weight of the
+    atom's ego-net within its molecule; None with useAtt = 0), ``lam_rank`` /
+    ``alpha_rank`` (int32 position inside the molecule by descending key, ties
+    by ascending id, 0 = largest) and ``core_mask`` (bool).  ``core``: the
+    graph core as a GraphBatch (``core.ndata["_ID"]`` = original node ids).
+    ``centres`` / ``weights`` [B, top_m]: the atoms whose ego-nets carry the
+    largest attention, and their alpha (-1 / 0 past a molecule's size; None
+    when ``top_m`` = 0).  ``ego``: the step's ego batch; the atoms of the
+    ego-net of centre c are ``ego.ndata["_ID"][ego.graph_ptr[c] :
+    ego.graph_ptr[c + 1]]``."""
+
+    __slots__ = ("lam", "alpha", "lam_rank", "alpha_rank", "core", "core_mask", "centres",
+                 "weights", "ego")
+
+    def __init__(self, **fields):
+        for name in self.__slots__:
+            setattr(self, name, fields[name])
+
+    def subgraph_nodes(self):
+        """Host convenience (synchronises: three device reads): per molecule the
+        list of (centre id, alpha, original node ids of the centre's ego-net)
+        of its significant subgraphs, in rank order."""
+        if self.centres is None:
+            raise ops._lib.ScgibError("subgraph_nodes: no significant subgraphs (top_m = 0)")
+        centres, weights = self.centres.cpu().tolist(), self.weights.cpu().tolist()
+        ptr, ids = self.ego.graph_ptr.cpu(), self.ego.ndata["_ID"].cpu()
+        return [[(c, w, ids[int(ptr[c]):int(ptr[c + 1])].tolist())
+                 for c, w in zip(cs, ws) if c >= 0] for cs, ws in zip(centres, weights)]
+
+
+def _explain(who, enc_owner, transfer, k, batch_g, batch_x, flatten_batch_subgraphs, x_subs,
+             ratio, threshold, top_m, u_gate, with_core=True):
+    """``explain`` of the four model classes: the eval forward of ``enc_owner``
+    (the module their forward hands ``_extract``) up to the interaction, then
+    ops.explain_rank and ops.core_subgraph (``with_core`` False, the dataset
+    pass: no core, ``core`` / ``core_mask`` None).  Moves no state: no
+    BatchNorm buffer (eval mode is required), no noise draw."""
+    if who.training or enc_owner.training:
+        raise RuntimeError("explain() needs model.eval(): a train-mode forward would move the "
+                           "BatchNorm running statistics")
+    if not batch_x.is_cuda:
+        raise ops._lib.ScgibError(f"explain: features on {batch_x.device}; the S-CGIB ops run on "
+                                  "the HIP device only (no CPU fallback)")
+    use_att = bool(enc_owner.useAtt)
+    top_m = int(top_m or 0)
+    if top_m and not use_att:
+        raise ValueError("explain: top_m >= 1 asks for significant subgraphs, but the model has "
+                         "no attention (useAtt = 0); pass top_m=0")
+    with torch.no_grad():
+        batch_g = G.as_graph_batch(batch_g)
+        if flatten_batch_subgraphs is None:
+            ego = G.egonet_batch(batch_g, k)
+        else:
+            ego = G.as_graph_batch(flatten_batch_subgraphs)
+        if x_subs is None:
+            x_subs = batch_x.index_select(0, ego.ndata["_ID"])
+        graph_features = enc_owner.Encoder1(batch_g, transfer(batch_x))
+        sub_readout = ops.segment_sum(enc_owner.Encoder2(ego, transfer(x_subs)), ego.graph_ptr,
+                                      ego.batch_size, ego.seg_dims)
+        lam, logit = ops.interaction_gates(graph_features, sub_readout, u_gate,
+                                           enc_owner.compressor, enc_owner.attn_layer, batch_g,
+                                           False, use_att)
+        alpha, lam_rank, alpha_rank, centres, weights = ops.explain_rank(lam, logit, batch_g, top_m)
+        core = core_mask = None
+        if with_core:
+            core, core_mask = ops.core_subgraph(lam, lam_rank, batch_g,
+                                                None if threshold is not None else ratio,
+                                                threshold)
+    return Explanation(lam=lam, alpha=alpha, lam_rank=lam_rank, alpha_rank=alpha_rank, core=core,
+                       core_mask=core_mask, centres=centres, weights=weights, ego=ego)
+
+
+def _explain_route(model):
+    """(encoder owner, transfer_d, k) that ``model.explain`` runs: the module
+    its forward hands ``_extract``, with the model's own transfer_d."""
+    if isinstance(model, Mainmodel):
+        return model, model.transfer_d, model.k_transition
+    if isinstance(model, (Mainmodel_continue, Mainmodel_domainadapt)):
+        return model.model, model.transfer_d, model.k_transition
+    if isinstance(model, Mainmodel_finetuning):
+        return model.model, model.transfer_d, getattr(model.model, "k_transition",
+                                                      model.k_transition)
+    raise TypeError(f"explain: {type(model).__name__} is none of the four S-CGIB model classes")
+
+
+class _Explainable:
+    """``explain`` of the four model classes."""
+
+    def explain(self, batch_g, batch_x, flatten_batch_subgraphs=None, x_subs=None, *, ratio=0.5,
+                threshold=None, top_m=3, u_gate=None):
+        """Graph core and significant subgraphs of a batch.
+
+        Runs the eval-mode forward up to the interaction under no_grad and
+        returns an ``Explanation``.  ``ratio`` in (0, 1] keeps the
+        ``max(1, ceil(n_i * ratio))`` atoms of largest gate per molecule;
+        ``threshold`` (replaces ratio) keeps the atoms with lam >= threshold.
+        ``top_m``: significant subgraphs per molecule (0: none; with useAtt = 0
+        anything else raises).  ``u_gate`` [N]: the gate draw; None is 0.5
+        everywhere, the median gate, which makes the result deterministic.
+        Needs ``model.eval()``; leaves state_dict() and the device noise state
+        bitwise unchanged.  Graph arguments as in ``forward``."""
+        return _explain(self, *_explain_route(self), batch_g, batch_x, flatten_batch_subgraphs,
+                        x_subs, ratio, threshold, top_m, u_gate)
+
+
+class _SCGIBCore(_Explainable, nn.Module):
     """Shared hot-path logic of Mainmodel / Mainmodel_continue."""
 
     def _prepare_ego(self, batch_g, flatten_batch_subgraphs, batch_x, x_subs):
@@ -1019,7 +1126,7 @@ class Mainmodel_domainadapt(_SCGIBCore):
 # ---------------------------------------------------------------------------
 # Fine-tuning head (boundary §8(b))
 # ---------------------------------------------------------------------------
-class Mainmodel_finetuning(nn.Module):
+class Mainmodel_finetuning(_Explainable, nn.Module):
     """models.py:358-543: a pretrained model's extract_features (frozen except
     the reference's freezing quirk) -> MLP -> Set2Set -> predict [-> sigmoid].
 

@@ -1971,10 +1971,12 @@ def class_loss(scores, labels, epoch=None, return_stats=False):
 # A6-A8: fused core <-> subgraph interaction
 # ---------------------------------------------------------------------------
 def _interaction_forward(ctx, f, t, s, u_gate, u_feat, gamma, beta, w2, b2, w_att, b_att, graph,
-                         bn, training, use_att=True):
+                         bn, training, use_att=True, gates_only=False):
     """Launch scgib_interaction_fwd (+ the BN running update); stores on ctx
     what the backward needs and returns (outputs, tensors to save).
-    ``use_att`` False: the kernels without the attention (the _v2 entries)."""
+    ``use_att`` False: the kernels without the attention (the _v2 entries).
+    ``gates_only`` (interaction_gates): the same launch, but no running-
+    statistics update and nothing kept for a backward."""
     u_gate, u_feat = _f32(u_gate, "interaction"), _f32(u_feat, "interaction")
     n, d = f.shape
     if d != HIDDEN:
@@ -2012,6 +2014,9 @@ def _interaction_forward(ctx, f, t, s, u_gate, u_feat, gamma, beta, w2, b2, w_at
     else:
         _launch("scgib_interaction_fwd_v2", {"n": n, "B": B}, *fwd_args, 0, st)
     ctx.use_att = bool(use_att)
+    if gates_only:
+        return (im, z1, z2, kl, kl_mean), (f, t, s, u_feat, gamma, beta, w2, w_att, z1, lam, logit,
+                                           stats)
     if training and bn.track_running_stats:
         nbt = bn.num_batches_tracked
 
@@ -2165,6 +2170,195 @@ def interaction_lin(f, s, u_gate, u_feat, compressor, attn, graph, training, use
     return _InteractionLin.apply(f, lin0.weight, lin0.bias, s, u_gate, u_feat, bn.weight, bn.bias,
                                  lin2.weight, lin2.bias, attn.weight, attn.bias, graph, bn,
                                  bool(training), bool(use_att))
+
+
+# ---------------------------------------------------------------------------
+# Graph cores and significant subgraphs (csrc/explain.hip)
+# ---------------------------------------------------------------------------
+class _NoCtx:
+    """Stands in for an autograd ctx where nothing is kept for a backward."""
+
+
+def interaction_gates(f, s, u_gate, compressor, attn, graph, training, use_att=True):
+    """(lam [N], logit [N]): the preservation gate and the attention logit of
+    every atom — the very tensors the interaction forward of the same inputs
+    saves for its backward, from the same launch (scgib_linear_fwd, then
+    scgib_interaction_fwd), without autograd.
+
+    ``lam_v = sigmoid(log(eps) - log(1 - eps) + p_v)`` with ``eps = 0.9999 -
+    0.9998 u_gate_v`` and ``p = compressor(f)`` per molecule, the compressor
+    BatchNorm on the molecule's batch statistics (``training``) or on its
+    running statistics.  ``u_gate=None``: 0.5 everywhere, the median gate
+    (sigmoid(p) up to the rounding of eps), deterministic.  ``logit`` is the
+    part of the attention logit that differs inside a molecule (w_hi . s_v);
+    with ``use_att`` False no logit exists and None is returned for it.
+
+    Unlike ops.interaction_lin this moves no state: no running-statistics
+    update of the compressor BatchNorm in either mode, and no draw from the
+    device noise stream (the feature noise only enters outputs that are not
+    returned)."""
+    with torch.no_grad():
+        f, s = _f32(f, "interaction_gates"), _f32(s, "interaction_gates")
+        n = f.shape[0]
+        if u_gate is None:
+            u_gate = torch.full((n,), 0.5, dtype=torch.float32, device=f.device)
+        u_gate = _f32(u_gate.reshape(-1), "interaction_gates")
+        if u_gate.shape[0] != n or s.shape != f.shape:
+            raise _lib.ScgibError(f"interaction_gates: f {tuple(f.shape)}, s {tuple(s.shape)}, "
+                                  f"u_gate {tuple(u_gate.shape)}")
+        lin0, bn, lin2 = compressor[0], compressor[1], compressor[3]
+        w0, b0 = _f32(lin0.weight, "compressor.0.weight"), _f32(lin0.bias, "compressor.0.bias")
+        if f.shape[1] != HIDDEN or tuple(w0.shape) != (HIDDEN, HIDDEN):
+            raise _lib.ScgibError("compressor[0] must be Linear(64, 64)")
+        t = torch.empty_like(f)
+        _lib.call("scgib_linear_fwd", _p(f), n, _p(w0), _p(b0), _p(t), _p(graph.dims), _stream())
+        # (f stands in for the feature noise: [N, 64] floats that lam and logit never see)
+        _, saved = _interaction_forward(_NoCtx(), f, t, s, u_gate, f, bn.weight, bn.bias,
+                                        lin2.weight, lin2.bias, attn.weight, attn.bias, graph, bn,
+                                        bool(training), bool(use_att), gates_only=True)
+    lam, logit = saved[9], saved[10]
+    return lam, (logit if use_att else None)
+
+
+def _explain_graph(who, graph, *tensors):
+    if graph.device.type != "cuda" or any(t is not None and not t.is_cuda for t in tensors):
+        raise _lib.ScgibError(f"{who}: the S-CGIB ops run on the HIP device only (no CPU fallback)")
+    n = graph.num_nodes()
+    for t in tensors:
+        if t is not None and tuple(t.shape) != (n,):
+            raise _lib.ScgibError(f"{who}: a per-atom tensor of {tuple(t.shape)} on a graph of "
+                                  f"{n} rows")
+    return n
+
+
+def explain_rank(lam, logit, graph, top_m=0):
+    """(alpha, lam_rank, alpha_rank, centres, weights) of a batch, one launch.
+
+    ``alpha`` [N] = softmax of ``logit`` over the atoms of each molecule (max,
+    sum, normalise in fp32, fixed order: bitwise reproducible).  ``lam_rank`` /
+    ``alpha_rank`` [N] int32: the position of an atom inside its molecule by
+    descending key, ties by ascending node id; keys compare as floats (-0.0
+    ties with +0.0), NaN sorts after every number, NaNs among themselves by id;
+    0 = largest.  ``centres`` / ``weights`` [B, top_m] (int32 / fp32): the
+    global ids and alpha of the atoms with alpha_rank < top_m, in rank order;
+    -1 / 0 past a molecule's size.  ``logit`` None (useAtt = 0): alpha,
+    alpha_rank, centres and weights are None and ``top_m`` must be 0.
+    Capacity mode: rows past the actual count get alpha 0 and ranks -1."""
+    n = _explain_graph("explain_rank", graph, lam, logit)
+    top_m = int(top_m)
+    if top_m < 0 or (top_m > 0 and logit is None):
+        raise _lib.ScgibError("explain_rank: top_m >= 1 needs the attention logit (useAtt = 1)"
+                              if top_m > 0 else "explain_rank: top_m below 0")
+    lam = _f32(lam, "explain_rank")
+    dev, B, i32 = lam.device, graph.batch_size, torch.int32
+    lam_rank = torch.empty(n, dtype=i32, device=dev)
+    alpha = alpha_rank = centres = weights = None
+    if logit is not None:
+        logit = _f32(logit, "explain_rank")
+        alpha = torch.empty(n, dtype=torch.float32, device=dev)
+        alpha_rank = torch.empty(n, dtype=i32, device=dev)
+        if top_m:
+            centres = torch.empty(B, top_m, dtype=i32, device=dev)
+            weights = torch.empty(B, top_m, dtype=torch.float32, device=dev)
+    _launch("scgib_explain_rank", {"n": n, "B": B}, _p(lam), _p(logit), _p(graph.graph_ptr), B, n,
+            top_m, _p(alpha), _p(lam_rank), _p(alpha_rank), _p(centres), _p(weights),
+            int(graph.dims is not None), _stream())
+    return alpha, lam_rank, alpha_rank, centres, weights
+
+
+def core_subgraph(lam, lam_rank, graph, ratio=None, threshold=None):
+    """(core, core_mask): the graph core of every molecule as one GraphBatch.
+
+    Exactly one rule: ``ratio`` in (0, 1] keeps the atoms with ``lam_rank <
+    max(1, ceil(n_i * ratio))`` (evaluated in IEEE double on the device);
+    ``threshold`` keeps the atoms with ``lam >= float32(threshold)`` (NaN is
+    never kept, a molecule may keep none).  The core is the subgraph induced
+    on the kept atoms with dgl.node_subgraph semantics: rows in ascending
+    original id, each row's columns in the original CSR order, filtered and
+    relabelled; ``graph_ptr`` over the kept counts (a molecule without a kept
+    atom becomes an empty graph); ``core.ndata["_ID"]`` = the original global
+    node ids (int32).  ``core_mask`` [N] bool.  Eager mode reads the core's two
+    totals once to size it; capacity mode (``graph.dims``) reads nothing back:
+    the core is sized by the graph's capacities, its actual sizes are in
+    ``core.dims`` and rows past them are empty."""
+    if (ratio is None) == (threshold is None):
+        raise ValueError("core_subgraph: exactly one of ratio and threshold")
+    if ratio is not None and not 0.0 < float(ratio) <= 1.0:
+        raise ValueError(f"core_subgraph: ratio {ratio} outside (0, 1]")
+    n = _explain_graph("core_subgraph", graph, lam, lam_rank)
+    lam = _f32(lam, "core_subgraph")
+    if lam_rank.dtype != torch.int32:
+        raise _lib.ScgibError(f"core_subgraph: lam_rank of {lam_rank.dtype}; int32")
+    lam_rank = lam_rank.contiguous()
+    dev, B, i32 = lam.device, graph.batch_size, torch.int32
+    pad = graph.dims is not None
+    mask = torch.empty(n, dtype=torch.bool, device=dev)
+    _launch("scgib_explain_core_mask", {"n": n, "B": B}, _p(lam), _p(lam_rank),
+            _p(graph.graph_ptr), B, n, 0 if ratio is not None else 1,
+            float(ratio) if ratio is not None else 1.0,
+            float(threshold) if threshold is not None else 0.0, _p(mask), int(pad), _stream())
+    err = torch.zeros(1, dtype=i32, device=dev)
+    words = int(_lib.query("scgib_explain_core_ws_words", n))
+
+    def compact(rowptr, col, gptr_out, ids, sizes):
+        ws = torch.empty(words, dtype=i32, device=dev)
+        core_dims = torch.empty(2, dtype=i32, device=dev)
+        _launch("scgib_explain_core_count", {"n": n}, _p(mask), _p(rowptr), _p(col), n, _p(ws),
+                _p(core_dims), _p(err), _p(graph.dims), _stream())
+        if sizes is None:
+            if pad:  # sized by the capacities, nothing read back
+                sizes = (n, int(col.shape[0]))
+            else:  # eager: the two totals (and the error word), one read
+                tot = torch.cat([core_dims, err]).cpu().tolist()
+                if tot[2]:
+                    raise _lib.ScgibError("core_subgraph: the core's size does not fit int32")
+                sizes = (int(tot[0]), int(tot[1]))
+        n_c, e_c = sizes
+        out_rowptr = torch.empty(n_c + 1, dtype=i32, device=dev)
+        out_col = torch.empty(max(e_c, 1), dtype=i32, device=dev)
+        out_id = torch.empty(max(n_c, 1), dtype=i32, device=dev) if ids else None
+        gp = torch.empty(B + 1, dtype=i32, device=dev) if gptr_out else None
+        _launch("scgib_explain_core_fill", {"n": n, "B": B}, _p(mask), _p(rowptr), _p(col),
+                _p(graph.graph_ptr), B, n, _p(ws), _p(core_dims), _p(out_rowptr), _p(out_col),
+                _p(out_id), _p(gp), n_c, max(e_c, 1), _p(graph.dims), _stream())
+        return out_rowptr, out_col[:e_c] if not pad else out_col, out_id, gp, core_dims, sizes
+
+    rowptr, col, out_id, gp, core_dims, sizes = compact(graph.rowptr, graph.col, True, True, None)
+    rp_t = col_t = None
+    if not graph.symmetric:  # the out-CSR of the same kept rows
+        rp_t, col_t = compact(graph.rowptr_t, graph.col_t, False, False, sizes)[:2]
+    core = _graph.GraphBatch(rowptr, col, gp, None, None, rp_t, col_t,
+                             max_graph_nodes=graph.max_graph_nodes,
+                             n_edges=-1 if pad else sizes[1])
+    core.dims = core_dims if pad else None
+    core.components_closed = graph.components_closed
+    dict.__setitem__(core.ndata, "_ID", out_id[:sizes[0]])
+    return core, mask
+
+
+def explain_store(lam, alpha, lam_rank, alpha_rank, graph, ids, node_off, out):
+    """Write a batch's per-atom rows into dataset-wide arrays: the rows of
+    molecule g go to ``node_off[ids[g]]`` of ``out`` = (lam, alpha, lam_rank,
+    alpha_rank) [total_nodes]; molecules with id -1 (the eval loader's fill)
+    are skipped.  ``alpha`` None: only lam and lam_rank.  One launch, no
+    atomics (a pass holds each molecule once), capturable."""
+    _explain_graph("explain_store", graph, lam, alpha, lam_rank, alpha_rank)
+    if ids.dtype != torch.int32 or node_off.dtype != torch.int64 or \
+            ids.numel() != graph.batch_size:
+        raise _lib.ScgibError("explain_store: ids int32 [B], node_off int64 [M + 1]")
+    o_lam, o_alpha, o_lr, o_ar = out
+    total = int(o_lam.shape[0])
+    for t, dt in ((o_lam, torch.float32), (o_lr, torch.int32)) + \
+            (((o_alpha, torch.float32), (o_ar, torch.int32)) if alpha is not None else ()):
+        if t is None or t.dtype != dt or tuple(t.shape) != (total,) or not t.is_contiguous() \
+                or t.device != lam.device:
+            raise _lib.ScgibError("explain_store: dataset arrays are contiguous [total_nodes] "
+                                  "fp32 / int32 on the batch's device")
+    _launch("scgib_explain_store", {"B": graph.batch_size}, _p(lam), _p(alpha), _p(lam_rank),
+            _p(alpha_rank), _p(graph.graph_ptr), graph.batch_size, _p(ids.contiguous()),
+            _p(node_off.contiguous()), int(node_off.numel()) - 1, total, _p(o_lam),
+            _p(o_alpha if alpha is not None else None), _p(o_lr),
+            _p(o_ar if alpha is not None else None), _stream())
 
 
 # ---------------------------------------------------------------------------
