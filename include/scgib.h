@@ -669,6 +669,9 @@ int scgib_egonet_k1_build_deg(const int32_t *rowptr, const int32_t *col, int64_t
  * e_cap columns is dropped and ORs the flag value 4 (bit 2; flags 1 and 2
  * as above) into *err (err may be NULL). */
 int64_t scgib_egonet_k1_scan_words(int64_t n_nodes);
+/* Launches of up to this many blocks (64 parents each) index the look-back by
+ * blockIdx.x; larger ones take each block's logical index from a ticket. */
+int64_t scgib_egonet_k1_resident_blocks(void);
 int scgib_egonet_k1_build_onepass(const int32_t *rowptr, const int32_t *col, int64_t n_nodes,
                                   int32_t max_in_degree, int32_t *ego_ptr, int32_t *ego_eptr,
                                   uint32_t *scan_state, int32_t *ego_nodes, int32_t *sub_rowptr,

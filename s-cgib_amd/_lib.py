@@ -94,6 +94,7 @@ SIGNATURES = {
     "scgib_egonet_k1_build_deg": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I64,
                                                  _P, _P, _P]),
     "scgib_egonet_k1_scan_words": (_I64, [_I64]),
+    "scgib_egonet_k1_resident_blocks": (_I64, []),
     "scgib_egonet_count_pool": (ctypes.c_int, [_P, _I32, _P, _I64, _I64, _I64, _I64, _I64, _I64,
                                                _I32, _I32, _P, _P, _P, _P, _P]),
     "scgib_egonet_fill_pool": (ctypes.c_int, [_P, _I32, _P, _I64, _I64, _I64, _I64, _I64, _I64,

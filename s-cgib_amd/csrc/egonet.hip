@@ -946,6 +946,9 @@ extern "C" int64_t scgib_egonet_k1_scan_words(int64_t n_nodes) {
     return 2 * ((n_nodes + kK1Block - 1) / kK1Block) + 4;
 }
 
+// grids of more blocks (of 64 parents) than this take the one-pass builder's ticket path
+extern "C" int64_t scgib_egonet_k1_resident_blocks(void) { return kK1Resident; }
+
 static int k1_onepass_launch(const int32_t *rowptr, const int32_t *col, int64_t n_nodes,
                              int32_t max_in_degree, int32_t *ego_ptr, int32_t *ego_eptr,
                              uint32_t *scan_state, int32_t *ego_nodes, int32_t *sub_rowptr,

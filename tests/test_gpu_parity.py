@@ -122,7 +122,9 @@ def test_egonet_synthetic_bit_exact(pkg, dev, workload, k):
 
 
 def test_egonet_large_molecules_multiword_bitmaps(pkg, dev):
-    # graphs of 100-400 atoms exercise the 2-, 4- and 8-word bitmaps
+    # graphs of 100-400 atoms: the batch's largest has more than 256, so every
+    # ball here is an 8-word bitmap (W = 8); W = 2 and W = 4 run in
+    # tests/test_gpu_ego_edges.py
     mols = pkg.synth.molecules(24, "qm9", seed=4, mu=250.0, sigma=90.0)
     gh, _ = pkg.graph.collate_pyg(mols)
     assert gh.max_graph_nodes > 256
