@@ -564,7 +564,14 @@ int scgib_gin_bwd_stats_z(const float *dz1, const int32_t *rowptr_t, const int32
  * With dw_ih, dw_hh, db_ih and db_hh all NULL, scgib_set2set_bwd writes dx and
  * dgates only, and scgib_set2set_wgrad (the same save / dgates) forms the
  * weight gradients later — the fine-tune step runs it off the critical
- * chain (ops.SlabScope). */
+ * chain (ops.SlabScope).
+ * Weight alignment: the kernels read a weight row as 16-byte vectors when it
+ * is a multiple of 4 floats.  scgib_set2set_fwd, _bwd, _fwd2 and _bwd2 (the
+ * entry points that take the weights; _wgrad and _save_floats take none)
+ * return SCGIB_EINVAL before any launch when w_ih is not 16-byte aligned and
+ * 2 dim % 4 == 0, or w_hh is not 16-byte aligned and dim % 4 == 0 — dim = 64
+ * (weights preloaded into registers) included.  ops.set2set / set2set_pair
+ * pass an aligned copy of such a weight. */
 int64_t scgib_set2set_save_floats(int64_t n_graphs, int32_t dim, int32_t n_iters);
 int scgib_set2set_fwd(const float *x, const int32_t *graph_ptr, int64_t n_graphs, int32_t dim,
                       int32_t n_iters, const float *w_ih, const float *b_ih, const float *w_hh,

@@ -62,7 +62,8 @@ __device__ __forceinline__ float s2s_sigmoid(float v) { return 1.f / (1.f + expf
 
 // <w[0, n), v[0, n)>, w a weight row in global memory, v in LDS: float4 loads
 // when the row is a multiple of 4 floats (it is then 16-B aligned: row j
-// starts at j n), four accumulators, unrolled so the row's loads are in
+// starts at j n from a 16-B aligned base, which the entry points require:
+// s2s_weights_aligned), four accumulators, unrolled so the row's loads are in
 // flight together (a latency-bound dot: one thread per gate)
 __device__ __forceinline__ float s2s_dot(const float *__restrict__ w, const float *v, int n) {
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
@@ -647,6 +648,16 @@ extern "C" int64_t scgib_set2set_save_floats(int64_t n_graphs, int32_t dim, int3
     return n_graphs * n_iters * s2s_save(dim);
 }
 
+// s2s_dot and the REG preload read a weight row as float4 when it is a multiple
+// of 4 floats (w_ih rows hold 2 dim, w_hh rows dim): row j then starts 16-B
+// aligned only if the base does.  Both directions refuse a base that is not,
+// before any launch, so a forward and its backward accept the same weights.
+static bool s2s_weights_aligned(const float *w_ih, const float *w_hh, int32_t dim) {
+    const bool ih4 = (2 * dim) % 4 == 0, hh4 = dim % 4 == 0;
+    return !(ih4 && (reinterpret_cast<uintptr_t>(w_ih) & 15)) &&
+           !(hh4 && (reinterpret_cast<uintptr_t>(w_hh) & 15));
+}
+
 // nin = 1 (xb, dxb unused) or 2 inputs
 static int s2s_launch_fwd(const float *xa, const float *xb, int nin, const int32_t *graph_ptr,
                           int64_t n_graphs, int32_t dim, int32_t n_iters, const float *w_ih,
@@ -657,6 +668,7 @@ static int s2s_launch_fwd(const float *xa, const float *xb, int nin, const int32
     if (nin * n_graphs > 0x7fffffff) return SCGIB_EUNSUPPORTED;
     if (!xa || !xb || !graph_ptr || !w_ih || !b_ih || !w_hh || !b_hh || !save || !out)
         return SCGIB_EINVAL;
+    if (!s2s_weights_aligned(w_ih, w_hh, dim)) return SCGIB_EINVAL;
     const unsigned grid = static_cast<unsigned>(nin * n_graphs);
     if (dim == kS2SMaxD)
         set2set_fwd_k<true><<<grid, 256, 0, as_stream(stream)>>>(
@@ -683,6 +695,7 @@ static int s2s_launch_bwd(const float *xa, const float *xb, int nin, const int32
     if (!xa || !xb || !graph_ptr || !w_ih || !w_hh || !save || (!g_outa && !g_outb) || !dxa ||
         !dxb || !dgates || (wg && (!dw_ih || !dw_hh || !db_ih || !db_hh)))
         return SCGIB_EINVAL;
+    if (!s2s_weights_aligned(w_ih, w_hh, dim)) return SCGIB_EINVAL;
     hipStream_t st = as_stream(stream);
     const int64_t nseg = nin * n_graphs;
     const int64_t tail = (n_rows * dim + 256 * 16 - 1) / (256 * 16);  // padding-zero blocks

@@ -1578,6 +1578,14 @@ def sum_nodes_graph(graph, x):
     return segment_sum(x, graph.graph_ptr, graph.batch_size)
 
 
+def _aligned16(t):
+    """t, or a copy of it when its first element is not 16-byte aligned (a
+    contiguous view at a storage offset): the Set2Set kernels read weight rows
+    of a multiple of 4 floats as 16-byte vectors, and the library refuses a
+    misaligned base (include/scgib.h)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _lstm_wgrads(ctx, d, device):
     """(buffer, views, their pointer arguments, deferred?): the Set2Set LSTM's
     dW_ih, dW_hh, db_ih, db_hh as views of one buffer — autograd takes the views
@@ -1606,6 +1614,7 @@ class _Set2Set(torch.autograd.Function):
                                   f"{tuple(w_ih.shape)}, w_hh {tuple(w_hh.shape)}")
         ctx.leaves = (w_ih, b_ih, w_hh, b_hh)
         ctx.scope = _slab_scope_for(ctx.leaves)
+        w_ih, w_hh = _aligned16(w_ih), _aligned16(w_hh)
         save = torch.empty(max(int(_lib.query("scgib_set2set_save_floats", nseg, d, n_iters)), 1),
                            dtype=torch.float32, device=x.device)
         out = torch.empty(nseg, 2 * d, dtype=torch.float32, device=x.device)
@@ -1662,6 +1671,7 @@ class _Set2SetPair(torch.autograd.Function):
                                   f"{tuple(w_hh.shape)}")
         ctx.leaves = (w_ih, b_ih, w_hh, b_hh)
         ctx.scope = _slab_scope_for(ctx.leaves)
+        w_ih, w_hh = _aligned16(w_ih), _aligned16(w_hh)
         save = torch.empty(max(int(_lib.query("scgib_set2set_save_floats", 2 * nseg, d, n_iters)),
                                1), dtype=torch.float32, device=xa.device)
         out = torch.empty(2, nseg, 2 * d, dtype=torch.float32, device=xa.device)
