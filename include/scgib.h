@@ -1579,6 +1579,78 @@ int scgib_explain_store(const float *lam, const float *alpha, const int32_t *lam
                         const int32_t *ids, const int64_t *node_off, int64_t n_molecules,
                         int64_t total_nodes, float *ds_lam, float *ds_alpha, int32_t *ds_lam_rank,
                         int32_t *ds_alpha_rank, scgib_stream_t stream);
+
+/* Molecule-resident eval forward (infer.hip; ops.infer_forward, infer.Scorer,
+ * DESIGN.md §29).  Entry points only: the ABI version does not change.
+ *
+ * One launch runs the whole eval-mode model (every BatchNorm on its running
+ * statistics) per molecule in LDS: transfer_d, Encoder1 over the molecule,
+ * Encoder2 over its ego-nets (the ego batch graph.egonet_batch built: ego-net
+ * v <-> row v, rows ego_ptr[v] .. ego_ptr[v + 1] of ego_rowptr / ego_col /
+ * ego_id, ego_id = the parent row of an ego row), the interaction of
+ * scgib_interaction_fwd with training = 0, and with has_head the MLP
+ * (128 -> 64 -> 64) and Set2Set (n_iters rounds).  The parameter table is
+ * copied into the kernel arguments before the call returns.  All weights are
+ * nn.Linear's / nn.LSTM's [out][in]; GIN layer 0's w1 is [64][32], transfer
+ * [32][n_feat]; ope = 1 + eps of the GINConv; bn_eps serves every BatchNorm.
+ *
+ * x [n_rows][n_feat]; u_gate [n_rows], u_feat [n_rows][64]: the noise.
+ * Outputs: z1, z2 [n_graphs][64] (sum readouts of the noisy and the plain
+ * features) always; pooled [n_graphs][128] with has_head; lam, logit [n_rows]
+ * and im [n_rows][128] when not NULL (logit only with use_att).  dims
+ * (capacity mode, or NULL): dims[0] = the actual row count, n_rows then the
+ * capacity; molecules without rows write zero rows, rows of lam / logit / im
+ * past the count are zeros.  e_cap / ego_rows / ego_e_cap: the lengths of col,
+ * of ego_id (ego_rowptr: ego_rows + 1) and of ego_col; no index at or past
+ * them is dereferenced.  max_graph_nodes: the host's bound on a molecule's
+ * rows.  Supported: 1 <= n_layers <= SCGIB_INFER_MAX_LAYERS, 1 <= n_feat <= 16,
+ * max_graph_nodes <= scgib_infer_max_nodes(); anything else returns
+ * SCGIB_EUNSUPPORTED without a launch.  On the device, a molecule above
+ * scgib_infer_max_nodes() rows, a graph_ptr range that is no range of the
+ * batch's rows, an ego-net above scgib_infer_max_ego_rows()
+ * rows, or an index that leaves its molecule / ego tile sets *err to 1
+ * (sticky: never cleared here) and that molecule's output rows to NaN.
+ * The weight matrices (w1, w2, c0_w, mlp2_w, w_ih, w_hh) are read as 16-byte
+ * vectors and must be 16-byte aligned (SCGIB_EINVAL).  No atomics, nothing
+ * read back: the launch captures, is bitwise reproducible, and a molecule's
+ * outputs do not depend on the batch around it.
+ * scgib_infer_ego_tile_rows(): ego-nets are walked in tiles of whole ego-nets
+ * of at most this many rows; scgib_infer_max_workgroups(): the grid's bound
+ * (workgroup b takes molecules b, b + grid, ...). */
+#define SCGIB_INFER_MAX_LAYERS 8
+typedef struct {
+    const float *transfer;
+    /* [0]: Encoder1, [1]: Encoder2 */
+    const float *w1[2][SCGIB_INFER_MAX_LAYERS], *b1[2][SCGIB_INFER_MAX_LAYERS];
+    const float *w2[2][SCGIB_INFER_MAX_LAYERS], *b2[2][SCGIB_INFER_MAX_LAYERS];
+    const float *gamma[2][SCGIB_INFER_MAX_LAYERS], *beta[2][SCGIB_INFER_MAX_LAYERS];
+    const float *rmean[2][SCGIB_INFER_MAX_LAYERS], *rvar[2][SCGIB_INFER_MAX_LAYERS];
+    float ope[2][SCGIB_INFER_MAX_LAYERS];
+    const float *c0_w, *c0_b, *cbn_gamma, *cbn_beta, *cbn_rmean, *cbn_rvar, *c3_w, *c3_b;
+    const float *att_w;
+    const float *mlp0_w, *mlp0_b, *mlp2_w, *mlp2_b;
+    const float *w_ih, *w_hh, *b_ih, *b_hh;
+    float bn_eps;
+    int32_t n_layers, n_feat, n_iters, use_att, has_head;
+} scgib_infer_params;
+int64_t scgib_infer_max_nodes(void);
+int64_t scgib_infer_max_ego_rows(void);
+int64_t scgib_infer_ego_tile_rows(void);
+int64_t scgib_infer_max_workgroups(void);
+int scgib_infer_fwd(const scgib_infer_params *p, const float *x, int64_t n_rows,
+                    const int32_t *rowptr, const int32_t *col, int64_t e_cap,
+                    const int32_t *graph_ptr, int64_t n_graphs, const int32_t *dims,
+                    int64_t max_graph_nodes, const int32_t *ego_ptr, const int32_t *ego_rowptr,
+                    const int32_t *ego_col, const int32_t *ego_id, int64_t ego_rows,
+                    int64_t ego_e_cap, const float *u_gate, const float *u_feat, float *pooled,
+                    float *z1, float *z2, float *lam, float *logit, float *im, int32_t *err,
+                    scgib_stream_t stream);
+/* out[ids[g]][0, width) = src[g][0, width) for the molecules g of a batch whose
+ * id lies in [0, n_out) (infer.score_dataset / embed_dataset: the eval
+ * loader's fill rows, id -1, write nothing).  A pass holds each id once: one
+ * writer per element, no atomics, capturable. */
+int scgib_infer_store(const float *src, int64_t n_graphs, int32_t width, const int32_t *ids,
+                      int64_t n_out, float *out, scgib_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

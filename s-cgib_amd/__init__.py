@@ -18,6 +18,8 @@ Layout:
                the device-side score buffer and metrics of an epoch (also a package attribute)
   explain.py   graph cores and significant subgraphs over a whole dataset (explain_dataset);
                per batch: ``model.explain(...)`` on the four model classes
+  infer.py     scoring / embedding with a trained model (Scorer, score_dataset, embed_dataset):
+               the eval forward as one molecule-resident launch
   optim.py     one-launch device Adam (drop-in for torch.optim.Adam as the scripts use it)
   cache.py     on-disk CSR cache of a molecule dataset (replaces the pts/ pickles)
   refckpt.py   the reference's whole-module checkpoints, read weights-only
@@ -28,7 +30,7 @@ Layout:
 import importlib
 
 __all__ = ["graph", "ops", "models", "dgl", "dist", "synth", "metrics", "optim", "cache", "refckpt",
-           "metric_wrapper", "explain", "_lib"]
+           "metric_wrapper", "explain", "infer", "_lib"]
 
 
 _MODEL_NAMES = ("Transformer", "GraphTransformerLayer", "MultiHeadAttentionLayer")

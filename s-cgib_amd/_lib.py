@@ -246,6 +246,13 @@ SIGNATURES = {
                                                _I64, _I64, _P, _P]),
     "scgib_explain_store": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _P, _P, _P,
                                            _P, _P]),
+    "scgib_infer_max_nodes": (_I64, []),
+    "scgib_infer_max_ego_rows": (_I64, []),
+    "scgib_infer_ego_tile_rows": (_I64, []),
+    "scgib_infer_max_workgroups": (_I64, []),
+    "scgib_infer_fwd": (ctypes.c_int, [_P, _P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P,
+                                       _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "scgib_infer_store": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _P]),
 }
 
 
@@ -326,6 +333,25 @@ class IngestDesc(ctypes.Structure):
                 [(n, ctypes.c_int32) for n in
                  ("B", "F", "idx_bytes", "max_graph_nodes", "max_in_degree", "bidirect",
                   "skip_rule", "pad_")])
+
+
+INFER_MAX_LAYERS = 8
+_LAYER_PTRS = (ctypes.c_void_p * INFER_MAX_LAYERS) * 2
+
+
+class InferParams(ctypes.Structure):
+    """scgib_infer_params (include/scgib.h)."""
+    _fields_ = ([("transfer", ctypes.c_void_p)] +
+                [(n, _LAYER_PTRS) for n in
+                 ("w1", "b1", "w2", "b2", "gamma", "beta", "rmean", "rvar")] +
+                [("ope", (ctypes.c_float * INFER_MAX_LAYERS) * 2)] +
+                [(n, ctypes.c_void_p) for n in
+                 ("c0_w", "c0_b", "cbn_gamma", "cbn_beta", "cbn_rmean", "cbn_rvar", "c3_w",
+                  "c3_b", "att_w", "mlp0_w", "mlp0_b", "mlp2_w", "mlp2_b", "w_ih", "w_hh", "b_ih",
+                  "b_hh")] +
+                [("bn_eps", ctypes.c_float)] +
+                [(n, ctypes.c_int32) for n in
+                 ("n_layers", "n_feat", "n_iters", "use_att", "has_head")])
 
 
 # scgib_ingest_* error bits (SCGIB_INGEST_E* in include/scgib.h)

@@ -3626,3 +3626,195 @@ def rank_metrics(scores, targets, rows=None, err=None, workspace_bytes=256 << 20
         mark("scan")
     return {"auc": out[0], "ap": out[1], "rmse": out[2], "acc": out[3], "pos": counts[0],
             "neg": counts[1], "labelled": counts[2], "err": err}
+
+
+# ---------------------------------------------------------------------------
+# Molecule-resident eval forward (csrc/infer.hip)
+# ---------------------------------------------------------------------------
+_INFER_ERR = {}  # device index -> the sticky error word of scgib_infer_fwd
+
+
+def infer_limits():
+    """The resident kernel's limits: ``max_nodes`` (atoms of a molecule),
+    ``max_ego_rows`` (rows of one ego-net), ``ego_tile_rows``, ``max_workgroups``
+    (no GPU needed)."""
+    return {k: int(_lib.query("scgib_infer_" + k)) for k in
+            ("max_nodes", "max_ego_rows", "ego_tile_rows", "max_workgroups")}
+
+
+def infer_error_word(device):
+    """The device's sticky error word (int32 [1]): 1 once a molecule exceeded a
+    limit or carried an index outside its molecule at run time (its rows are
+    NaN).  Created zeroed at the first eager call."""
+    idx = torch.device(device).index or 0
+    w = _INFER_ERR.get(idx)
+    if w is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.ScgibError("infer_forward: run one eager call before the capture (the "
+                                  "error word is created there)")
+        w = _INFER_ERR[idx] = _zeroed_words(1, device)
+    return w
+
+
+def infer_error(device, reset=False):
+    """Whether a launch of scgib_infer_fwd on ``device`` met a molecule above a
+    limit or an index outside its molecule since the word was last reset (a
+    device read; such a molecule's rows are NaN).  The word is sticky: only
+    ``reset=True`` clears it.  Eager ``infer_forward`` / ``Scorer`` calls never
+    read it — nothing is read back in a call — so a caller who wants the
+    check asks here; ``infer.score_dataset`` / ``embed_dataset`` check their
+    own pass."""
+    w = infer_error_word(device)
+    flag = bool(int(w.item()))
+    if reset:
+        w.zero_()
+    return flag
+
+
+def infer_unsupported(enc1, enc2, transfer, compressor, n_feat=None):
+    """None when the resident kernel runs this model, else the reason (host
+    logic only): two fused GIN encoders of one depth 1..8 at width 64 over
+    d_transfer = 32, transfer_d without a bias, F <= 16."""
+    from . import models as _m
+    for e in (enc1, enc2):
+        if not isinstance(e, _m.GIN):
+            return f"a {type(e).__name__} encoder (the resident kernel runs GIN encoders)"
+        w = e.ginlayers[0].apply_func.mlp[0].weight
+        if tuple(w.shape) != (HIDDEN, 32) or not e.fused:
+            return f"a GIN of layer-0 weight {tuple(w.shape)} (hidden_dim 64 over d_transfer 32)"
+    if len(enc1.ginlayers) != len(enc2.ginlayers) or not 1 <= len(enc1.ginlayers) <= \
+            _lib.INFER_MAX_LAYERS:
+        return f"GIN depths {len(enc1.ginlayers)} / {len(enc2.ginlayers)} (one depth, 1..8)"
+    if transfer.bias is not None or transfer.out_features != 32:
+        return "a transfer_d with a bias or another width than 32"
+    if n_feat is None:
+        n_feat = transfer.in_features
+    if not 1 <= n_feat <= 16 or transfer.in_features != n_feat:
+        return f"{n_feat} raw feature columns (1..16, transfer_d's input width)"
+    if tuple(compressor[0].weight.shape) != (HIDDEN, HIDDEN):
+        return "a compressor of another width than 64"
+    return None
+
+
+class InferTable:
+    """scgib_infer_params of a model (and the tensors its pointers refer to)."""
+
+    def __init__(self, enc1, enc2, transfer, compressor, attn, use_att, mlp=None, s2s=None):
+        why = infer_unsupported(enc1, enc2, transfer, compressor)
+        if why is not None:
+            raise _lib.ScgibError(f"infer_forward: {why}")
+        keep = self.keep = []
+
+        def ptr(t, name, aligned=False):
+            t = _f32(t.detach(), name)
+            if aligned:
+                t = _aligned16(t)
+            keep.append(t)
+            return t.data_ptr()
+
+        P = self.params = _lib.InferParams()
+        P.transfer = ptr(transfer.weight, "transfer_d.weight")
+        eps = set()
+        for e, enc in enumerate((enc1, enc2)):
+            for l, (conv, bn) in enumerate(zip(enc.ginlayers, enc.batch_norms)):
+                mlp_l = conv.apply_func.mlp
+                for field, t in (("w1", mlp_l[0].weight), ("b1", mlp_l[0].bias),
+                                 ("w2", mlp_l[2].weight), ("b2", mlp_l[2].bias),
+                                 ("gamma", bn.weight), ("beta", bn.bias),
+                                 ("rmean", bn.running_mean), ("rvar", bn.running_var)):
+                    getattr(P, field)[e][l] = ptr(t, f"Encoder{e + 1} layer {l} {field}",
+                                                  field in ("w1", "w2"))
+                P.ope[e][l] = float(conv._one_plus_eps)
+                eps.add(float(bn.eps))
+        lin0, cbn, lin3 = compressor[0], compressor[1], compressor[3]
+        eps.add(float(cbn.eps))
+        if len(eps) != 1:
+            raise _lib.ScgibError(f"infer_forward: BatchNorm eps values {sorted(eps)} (one value)")
+        P.bn_eps = eps.pop()
+        P.c0_w, P.c0_b = ptr(lin0.weight, "compressor.0.weight", True), ptr(lin0.bias, "compressor.0.bias")
+        P.cbn_gamma, P.cbn_beta = ptr(cbn.weight, "compressor.1.weight"), ptr(cbn.bias, "compressor.1.bias")
+        P.cbn_rmean = ptr(cbn.running_mean, "compressor.1.running_mean")
+        P.cbn_rvar = ptr(cbn.running_var, "compressor.1.running_var")
+        P.c3_w, P.c3_b = ptr(lin3.weight, "compressor.3.weight"), ptr(lin3.bias, "compressor.3.bias")
+        P.use_att = int(bool(use_att))
+        if use_att:
+            if tuple(attn.weight.shape) != (1, 2 * HIDDEN):
+                raise _lib.ScgibError("infer_forward: attn_layer must be Linear(128, 1)")
+            P.att_w = ptr(attn.weight, "attn_layer.weight")
+        P.n_layers, P.n_feat = len(enc1.ginlayers), int(transfer.in_features)
+        P.has_head = int(mlp is not None)
+        if mlp is not None:
+            if tuple(mlp[0].weight.shape) != (HIDDEN, 2 * HIDDEN) or \
+                    tuple(mlp[2].weight.shape) != (HIDDEN, HIDDEN) or s2s is None or \
+                    s2s.input_dim != HIDDEN:
+                raise _lib.ScgibError("infer_forward: the head is MLP(128 -> 64 -> 64) and "
+                                      "Set2Set(64)")
+            P.mlp0_w, P.mlp0_b = ptr(mlp[0].weight, "MLP.0.weight"), ptr(mlp[0].bias, "MLP.0.bias")
+            P.mlp2_w, P.mlp2_b = ptr(mlp[2].weight, "MLP.2.weight", True), ptr(mlp[2].bias, "MLP.2.bias")
+            lstm = s2s.lstm
+            P.w_ih = ptr(lstm.weight_ih_l0, "lstm.weight_ih_l0", True)
+            P.w_hh = ptr(lstm.weight_hh_l0, "lstm.weight_hh_l0", True)
+            P.b_ih, P.b_hh = ptr(lstm.bias_ih_l0, "lstm.bias_ih_l0"), ptr(lstm.bias_hh_l0, "lstm.bias_hh_l0")
+            P.n_iters = int(s2s.n_iters)
+
+
+def infer_forward(x, graph, ego, table, u_gate, u_feat, rows=False):
+    """The eval-mode forward of ``table``'s model (an ops.InferTable) over a
+    batch, ONE launch (scgib_infer_fwd), no autograd: returns
+    ``(pooled [B, 128] or None, z1 [B, 64], z2 [B, 64], lam, logit, im)``,
+    the last three ([N], [N], [N, 128]; logit None without attention) only with
+    ``rows``, else None.  ``x`` [N, F] normalised raw features, ``graph`` /
+    ``ego`` the batch and its ego batch (graph.egonet_batch), ``u_gate`` [N] /
+    ``u_feat`` [N, 64] the noise.  Refuses CPU tensors and a batch whose host
+    bound ``graph.max_graph_nodes`` exceeds ``infer_limits()['max_nodes']``
+    without a launch.  Capacity mode (``graph.dims``): nothing is read back."""
+    with torch.no_grad():
+        if graph.device.type != "cuda" or not x.is_cuda:
+            raise _lib.ScgibError(f"infer_forward: features on {x.device}, graph on {graph.device}; "
+                                  "the S-CGIB ops run on the HIP device only (no CPU fallback)")
+        x, u_gate, u_feat = (_f32(x, "infer_forward x"), _f32(u_gate.reshape(-1), "u_gate"),
+                             _f32(u_feat, "u_feat"))
+        n, B, P = graph.num_nodes(), graph.batch_size, table.params
+        if x.dim() != 2 or x.shape[0] != n or x.shape[1] != P.n_feat or u_gate.shape[0] != n or \
+                tuple(u_feat.shape) != (n, HIDDEN):
+            raise _lib.ScgibError(f"infer_forward: x {tuple(x.shape)}, u_gate {tuple(u_gate.shape)}, "
+                                  f"u_feat {tuple(u_feat.shape)} on a graph of {n} rows, F = "
+                                  f"{P.n_feat}")
+        lim = infer_limits()
+        if graph.max_graph_nodes > lim["max_nodes"]:
+            raise _lib.ScgibError(f"infer_forward: a molecule of up to {graph.max_graph_nodes} atoms; "
+                                  f"the resident kernel holds {lim['max_nodes']}")
+        if ego.graph_ptr.shape[0] != n + 1:
+            raise _lib.ScgibError("infer_forward: the ego batch is not this graph's (one ego-net "
+                                  "per atom)")
+        dev, f32 = x.device, torch.float32
+        ego_id = ego.ndata["_ID"]
+        pooled = torch.empty(B, 2 * HIDDEN, dtype=f32, device=dev) if P.has_head else None
+        z1 = torch.empty(B, HIDDEN, dtype=f32, device=dev)
+        z2 = torch.empty(B, HIDDEN, dtype=f32, device=dev)
+        lam = logit = im = None
+        if rows:
+            lam = torch.empty(n, dtype=f32, device=dev)
+            logit = torch.empty(n, dtype=f32, device=dev) if P.use_att else None
+            im = torch.empty(n, 2 * HIDDEN, dtype=f32, device=dev)
+        _launch("scgib_infer_fwd", {"n": n, "B": B}, ctypes.byref(P), _p(x), n, _p(graph.rowptr),
+                _p(graph.col), int(graph.col.shape[0]), _p(graph.graph_ptr), B, _p(graph.dims),
+                int(graph.max_graph_nodes), _p(ego.graph_ptr), _p(ego.rowptr), _p(ego.col),
+                _p(ego_id), int(ego_id.shape[0]), int(ego.col.shape[0]), _p(u_gate), _p(u_feat),
+                _p(pooled), _p(z1), _p(z2), _p(lam), _p(logit), _p(im),
+                _p(infer_error_word(dev)), _stream())
+    return pooled, z1, z2, lam, logit, im
+
+
+def infer_store(src, ids, out):
+    """``out[ids[g]] = src[g]`` for the ids in [0, len(out)); the eval loader's
+    fill rows (-1) write nothing.  One launch, capturable."""
+    src = _f32(src, "infer_store")
+    if ids.dtype != torch.int32 or ids.numel() != src.shape[0] or out.dtype != torch.float32 or \
+            not out.is_contiguous() or out.dim() != 2 or out.shape[1] != src.shape[1] or \
+            out.device != src.device:
+        raise _lib.ScgibError("infer_store: ids int32 [B], out contiguous fp32 [M, width] on the "
+                              "batch's device")
+    _launch("scgib_infer_store", {"B": int(src.shape[0])}, _p(src), int(src.shape[0]),
+            int(src.shape[1]), _p(ids.contiguous()), int(out.shape[0]), _p(out), _stream())
+    return out
